@@ -9,14 +9,23 @@ training iteration over the device batch: forward, hand-derived backward,
 captured in one HIP graph and replayed.  Inputs are resident in HBM.
 
     python bench.py [--gpus N --steps K --warmup W --graphs-per-gpu B]
+    python bench.py --full ...           (everything beside the headline, below)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         bench.py --gpus N ...            (one rank per GPU, RCCL over xGMI)
 
 Prints ONE JSON line on rank 0.  value = graphs/sec over all ranks (weak
-scaling: B graphs per GPU).  roofline = the dominant kernel (fused zz^T + CE,
-MFMA-bound), timed with HIP events on the launch stream.  cpu_baseline = the
-reference formulation (dense A, materialised [N,N,2] logits, autograd, TF1
-Adam) in torch-CPU fp32 on the host cores (TensorFlow is unavailable).
+scaling: B graphs per GPU); ms_per_step = the median timed step.  A plain run
+sets up, warms up, times the K steps and prints that line.  --dump-outputs DIR
+also writes what the last timed step left its caller (loss terms, parameters,
+gradient, Adam moments) as DIR/<name>.npy; the inputs are the same in every
+run with the same arguments, so two builds compare output for output.
+
+--full adds what takes runs of its own: roofline = the dominant kernel (fused
+zz^T + CE, MFMA-bound), timed with HIP events on the launch stream, the SpMM
+secondary roofline, the fp32 mode, the one-graph (C3 per-rank) step, the batch
+sweep, the C4 / C5 workloads, and cpu_baseline = the reference formulation
+(dense A, materialised [N,N,2] logits, autograd, TF1 Adam) in torch-CPU fp32
+on the host cores (TensorFlow is unavailable).
 """
 from __future__ import annotations
 
@@ -498,6 +507,74 @@ def extra_workload(name, args, info):
     return res
 
 
+def rooflines(args, cfg, model, db, host):
+    """--full: the dominant kernels of the headline step, each timed in runs of its own
+    (time_launches) on the step's workspace: `roofline` (fused zz^T + CE) and
+    `secondary_roofline` (the SpMM)."""
+    B, N, d = args.graphs_per_gpu, args.nodes, args.latent
+    bc = db.c_struct()
+    kernel_ms = kernel_timer(model, bc, args.kernel_reps)
+
+    # ---- dominant kernel: fused zz^T + CE, HIP events on the launch stream
+    zzt_ms = kernel_ms("zzt_dense")
+    zzt_v1_ms = kernel_ms("zzt_dense_v1") if args.dtype == "bf16" else None
+    fast = args.dtype == "bf16"
+    spmm_ms = kernel_ms("spmm_bf16" if fast else "spmm_dxw1")
+    spmm_tiled_ms = kernel_ms("spmm_bf16_tiled") if fast and db.tiles else None
+    flops = 4.0 * N * N * d * B                       # 2N^2 d fwd + 2N^2 d bwd per graph
+    achieved = flops / (zzt_ms * 1e-3) / 1e12
+    peak = PEAK_TFLOPS[args.dtype]
+    h1 = cfg.g_conv_hidden[1]
+    # SURVEY 8d SpMM units: rowptr + colidx + feature rows in + out (bf16 on the fast path)
+    fb = 2 if fast else 4
+    spmm_bytes = 4 * (B * N + 1) + 4 * host.nnz + 2 * fb * B * N * h1
+    spmm_gbs = spmm_bytes / (spmm_ms * 1e-3) / 1e9
+
+    return {
+        "roofline": {"kernel": "zzt_dense (fused z z^T + CE fwd+bwd; " +
+                               ("zzt_dense_bf16_v9: two 512-thread workgroups per CU" if fast and d <= 64 and d > 32
+                                else "zzt_dense_bf16_v7" if fast and d > 64 else "v4 / fp32") + ")",
+                     "bound": "mfma",
+                     "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                     "frac": round(achieved / peak, 4),
+                     "traffic": load_traffic(N, d, B, args.dtype),
+                     "avg_launch_ms": round(zzt_ms, 5), "flops_per_launch": flops,
+                     "previous_variant_ms": None if zzt_v1_ms is None else round(zzt_v1_ms, 5)},
+        "secondary_roofline": dict(
+            spmm_batched(host, h1, args.spmm_copies, max(4, args.kernel_reps // 2)) if fast else {},
+            in_step={"kernel": f"csr_spmm (A @ dP1, width {h1}, {'bf16' if fast else 'fp32'}, "
+                               f"{B} graphs, "
+                               f"{'window' if fast and db.window else ('row tiles' if fast and db.tiles else 'register gathers')})",
+                     "achieved": round(spmm_gbs, 1), "frac": round(spmm_gbs / PEAK_HBM_GBS, 4),
+                     "avg_launch_ms": round(spmm_ms, 5), "bytes_per_launch": spmm_bytes,
+                     "row_tiles_ms": None if spmm_tiled_ms is None else round(spmm_tiled_ms, 5),
+                     "note": "8 graphs: a 4 MB working set, L2-resident; the HBM fraction is the 256-graph line"}),
+    }
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, model, opt):
+    """What the step just run left its caller, as path/<name>.npy: the loss terms
+    (float64, optimizer.LOSS_NAMES order) and the flat parameters, gradient and Adam
+    moments (float32, params.flat_layout order).  An array above its share of
+    DUMP_BYTES is written as a fixed sample: the elements at the sorted indices
+    numpy's default_rng(0) draws for its size."""
+    import numpy as np
+    pc = model.param_count
+    arrays = {"losses": opt.losses, "params": model.params[:pc], "grads": opt.grads[:pc],
+              "adam_m": opt.m[:pc], "adam_v": opt.v[:pc]}
+    share = DUMP_BYTES // len(arrays)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > share:
+            a = a[np.sort(np.random.default_rng(0).integers(0, a.size, share // a.itemsize))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -507,6 +584,13 @@ def main():
     ap.add_argument("--nodes", type=int, default=4096)
     ap.add_argument("--latent", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: kernel rooflines, fp32 and one-graph modes, batch "
+                         "sweep, the C4 / C5 workloads and the CPU baseline (each takes runs of "
+                         "its own; the options below them apply with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss terms, "
+                         "parameters, gradient, Adam moments) as DIR/<name>.npy")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP graph")
     ap.add_argument("--no-tiles", action="store_true", help="register-gather SpMM instead of LDS row tiles")
     ap.add_argument("--kernel-reps", type=int, default=20)
@@ -543,24 +627,8 @@ def main():
     timing = dict(TIMING)
     losses = opt.loss_dict(global_mean=True)
     log(f"[rank {info.rank}] {value:.1f} graphs/s, {ms:.3f} ms/step")
-
-    bc = db.c_struct()
-    kernel_ms = kernel_timer(model, bc, args.kernel_reps)
-
-    # ---- dominant kernel: fused zz^T + CE, HIP events on the launch stream
-    zzt_ms = kernel_ms("zzt_dense")
-    zzt_v1_ms = kernel_ms("zzt_dense_v1") if args.dtype == "bf16" else None
-    fast = args.dtype == "bf16"
-    spmm_ms = kernel_ms("spmm_bf16" if fast else "spmm_dxw1")
-    spmm_tiled_ms = kernel_ms("spmm_bf16_tiled") if fast and db.tiles else None
-    flops = 4.0 * N * N * d * B                       # 2N^2 d fwd + 2N^2 d bwd per graph
-    achieved = flops / (zzt_ms * 1e-3) / 1e12
-    peak = PEAK_TFLOPS[args.dtype]
-    h1 = cfg.g_conv_hidden[1]
-    # SURVEY 8d SpMM units: rowptr + colidx + feature rows in + out (bf16 on the fast path)
-    fb = 2 if fast else 4
-    spmm_bytes = 4 * (B * N + 1) + 4 * host.nnz + 2 * fb * B * N * h1
-    spmm_gbs = spmm_bytes / (spmm_ms * 1e-3) / 1e9
+    if args.dump_outputs and info.rank == 0:
+        dump_outputs(args.dump_outputs, model, opt)
 
     out = {
         "metric": METRIC,
@@ -585,29 +653,13 @@ def main():
                    "n_nodes": N, "latent": d, "graphs_per_gpu": B, "global_batch": B * info.world,
                    "nnz_per_graph": round(host.nnz / B, 1), "parallelism": f"dp{info.world}",
                    "hip_graph": not args.no_graph},
-        "roofline": {"kernel": "zzt_dense (fused z z^T + CE fwd+bwd; " +
-                               ("zzt_dense_bf16_v9: two 512-thread workgroups per CU" if fast and d <= 64 and d > 32
-                                else "zzt_dense_bf16_v7" if fast and d > 64 else "v4 / fp32") + ")",
-                     "bound": "mfma",
-                     "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4),
-                     "traffic": load_traffic(N, d, B, args.dtype),
-                     "avg_launch_ms": round(zzt_ms, 5), "flops_per_launch": flops,
-                     "previous_variant_ms": None if zzt_v1_ms is None else round(zzt_v1_ms, 5)},
-        "secondary_roofline": dict(
-            spmm_batched(host, h1, args.spmm_copies, max(4, args.kernel_reps // 2)) if fast else {},
-            in_step={"kernel": f"csr_spmm (A @ dP1, width {h1}, {'bf16' if fast else 'fp32'}, "
-                               f"{B} graphs, "
-                               f"{'window' if fast and db.window else ('row tiles' if fast and db.tiles else 'register gathers')})",
-                     "achieved": round(spmm_gbs, 1), "frac": round(spmm_gbs / PEAK_HBM_GBS, 4),
-                     "avg_launch_ms": round(spmm_ms, 5), "bytes_per_launch": spmm_bytes,
-                     "row_tiles_ms": None if spmm_tiled_ms is None else round(spmm_tiled_ms, 5),
-                     "note": "8 graphs: a 4 MB working set, L2-resident; the HBM fraction is the 256-graph line"}),
         "losses": {k: round(v, 6) for k, v in losses.items()},
     }
     from snd_vae_amd.build import lib_status
     out["build"] = lib_status()
-    if info.world == 1 and not args.no_modes:
+    if args.full:
+        out.update(rooflines(args, cfg, model, db, host))
+    if args.full and info.world == 1 and not args.no_modes:
         # the same step in the fp32 parity mode (generic engine), and C3's per-rank work:
         # one N=4096 graph per GPU (global batch 8 over 8 GPUs = strong scaling)
         del_models()
@@ -649,13 +701,13 @@ def main():
                                        warmup=min(args.warmup, 5))
             out["batch_sweep"][str(bs)] = {"value": round(vb, 3), "unit": "graphs/s", "ms_per_step": round(msb, 4)}
             del_models()
-    extra = [w for w in args.extra.split(",") if w] if info.world == 1 else []
+    extra = [w for w in args.extra.split(",") if w] if args.full and info.world == 1 else []
     if extra:
         out["workloads"] = {}
         for w in extra:
             out["workloads"][w] = extra_workload(w, args, info)
             del_models()
-    if info.rank == 0 and info.world == 1 and not args.no_cpu_baseline:
+    if args.full and info.rank == 0 and info.world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline(N, d, args.cpu_baseline_seconds)
     if info.rank == 0:

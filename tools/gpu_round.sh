@@ -14,12 +14,13 @@ timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun
 tail -1 gpurun_out/smoke.log
 echo "== torchrun world 1, forced all-reduce"
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 --force-dist --extra "" --no-cpu-baseline \
+  --master-port 29533 bench.py --gpus 1 --full --steps 20 --warmup 5 --force-dist --extra "" --no-cpu-baseline \
   > gpurun_out/bench_dist1.log 2>&1 || { echo "DIST BENCH FAILED"; tail -30 gpurun_out/bench_dist1.log; exit 1; }
 tail -1 gpurun_out/bench_dist1.log | cut -c1-300
 if [ -n "$BENCH" ]; then
   echo "== bench"
-  timeout -k 10 400 python -u bench.py > gpurun_out/bench.log 2>&1 || { echo "BENCH FAILED"; tail -30 gpurun_out/bench.log; exit 1; }
-  tail -1 gpurun_out/bench.log | cut -c1-400
+  blog=${BENCH_LOG:-bench_full.log}
+  timeout -k 10 400 python -u bench.py --full > "$blog" 2>&1 || { echo "BENCH FAILED"; tail -30 "$blog"; exit 1; }
+  tail -1 "$blog" | cut -c1-400
 fi
 echo "== done"

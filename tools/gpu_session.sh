@@ -23,10 +23,10 @@ for s in ${STAGES:-tests smoke ab bench timeline}; do
     tests) step pytest_gpu 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ;;
     smoke) step smoke 200 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     ab) step ab 400 python -u tools/ab_flags.py --flags ${ABFLAGS:-0,32768} --kernels ${ABKERN:-zzt_dense} ;;
-    bench) step bench 400 python -u bench.py ;;
+    bench) step bench 400 python -u bench.py --full ;;
     dist1) step bench_dist1 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
              --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 \
-             --force-dist --extra "" --no-cpu-baseline ;;
+             --full --force-dist --extra "" --no-cpu-baseline ;;
     timeline)
       for c in ${TLCONF:-C2}; do
         a=""; [ $c != C2 ] && a="--config $c"; [ $c == C5 ] && a="$a --graphs 1"
@@ -36,11 +36,11 @@ for s in ${STAGES:-tests smoke ab bench timeline}; do
         tail -3 gpurun_out/st/$c.timeline.txt
       done ;;
     prof) step rocprof 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run \
-             --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --extra "" ;;
+             --output-format csv -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --extra "" ;;
     profh) step rocprof_headline 400 rocprofv3 --kernel-trace --stats -d gpurun_out/profh -o run \
              --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --extra "" \
              --batch-sweep "" --no-modes ;;
-    benchq) step benchq 300 python -u bench.py --steps 50 --warmup 10 --no-cpu-baseline --batch-sweep "" --extra "" ;;
+    benchq) step benchq 300 python -u bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --batch-sweep "" --extra "" ;;
     traffic)   # per-kernel HBM bytes of eager C2 steps: one counter per rocprofv3 run
       step pmc_fetch 200 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o run --output-format csv \
         -- python tools/prof_step.py --steps 3
