@@ -142,6 +142,7 @@ def test_c2_bench_batch_steps_vs_oracle(dtype):
                                         batch.spatial_truth, eps[t - 1].astype(np.float64),
                                         cfg, row_chunk=1024)
         kinks = {}
+        rg_plain = rg        # the oracle's own derivative choice everywhere (e32 below)
         if dtype == "f32":   # lrelu' at pre-activations that are zero within fp32 rounding
             over, kinks = gpu_kink_choices(model, p, rc, cfg, B)
             if over:
@@ -177,9 +178,12 @@ def test_c2_bench_batch_steps_vs_oracle(dtype):
                                         "ambiguous": amb})
             if e > 1e-6 or abs(got["correct"] - correct) > amb:
                 fails.append((t, "own_structure", got["adj_sum"], ce, e, got["correct"], correct, amb))
-        else:                 # the fp32 conditioning of each block (reference formulation)
+        else:                 # the fp32 conditioning of each block (reference formulation),
+            # against the oracle's gradient WITHOUT the kink override: the torch-fp32 run makes
+            # its own derivative choice, so against the kink-aligned rg a tie would put the
+            # kink itself (2e-3 of dec.K1) into e32 and loosen the bar of exactly those blocks
             e32 = PB.e32_grads(p, [batch.dense_adj(b) for b in range(B)], batch.features,
-                               batch.feature_truth, batch.spatial_truth, eps[t - 1], cfg, rg)
+                               batch.feature_truth, batch.spatial_truth, eps[t - 1], cfg, rg_plain)
             bars.note("e32", e32)
         for k in p:
             e = block_err(gg[k], rg[k])

@@ -54,6 +54,31 @@ def test_own_structure_matches_dense_evaluation():
     assert abs(correct - ref_correct) <= amb
 
 
+def test_own_structure_reads_a_padded_staging_image():
+    """d = 16: the staging image is 32 columns wide, zero past d; a non-zero pad is an error."""
+    n, d, B = 130, 16, 2
+    cfg = tscale(n, d, mean_degree=8.0)
+    batch = synthetic_batch(cfg, B, seed=3)
+    z = np.random.default_rng(0).standard_normal((B * n, d)).astype(np.float32)
+    c = math.sqrt(1.0 / math.log(2.0))
+    img = torch.zeros(B, 256, 32, dtype=torch.bfloat16)
+    img[:, :n, :d] = (torch.from_numpy(z) * c).to(torch.bfloat16).view(B, n, d)
+    zb = torch.from_numpy(z).to(torch.bfloat16)
+    ce, absum, correct, amb = PB.own_structure(_FakeModel({"ZSTAGE": img.reshape(-1), "ZB": zb.reshape(-1)}),
+                                               batch, cfg)
+    ref_ce = 0.0
+    for b in range(B):
+        J = img[b, :n, :d].double().numpy()
+        Zb = zb[b * n:(b + 1) * n].double().numpy()
+        off = ~np.eye(n, dtype=bool)
+        ref_ce += float((R.softplus((J @ J.T) * math.log(2.0)) - batch.dense_adj(b) * (Zb @ Zb.T))[off].sum())
+        ref_ce += n * PB.SOFTPLUS_M1
+    assert ce == pytest.approx(ref_ce, rel=1e-12)
+    img[1, 3, d + 2] = 1.0
+    with pytest.raises(AssertionError, match="pad"):
+        PB.own_structure(_FakeModel({"ZSTAGE": img.reshape(-1), "ZB": zb.reshape(-1)}), batch, cfg)
+
+
 def test_e32_is_the_fp32_rounding_of_the_reference_formulation():
     n, d, B = 25, 16, 2
     cfg = tscale(n, d, mean_degree=4.0)
