@@ -72,7 +72,7 @@ int snd_csr_spmm(const int* rowptr, const int* colidx, int n_rows,
 
 /* a2 in the bf16 throughput mode (the SpMM of the fast path, layers.py:122 and
  * its backward): out = A @ h over bf16 rows with fp32 accumulation, rounded to
- * bf16.  width % 8 == 0 and <= 128; ldh, ldo % 8 == 0 (16-byte rows).  When
+ * bf16.  width % 8 == 0 in 8..128; ldh, ldo % 8 == 0 (16-byte rows).  When
  * n_per_graph % 32 == 0 and n_graphs % 8 == 0 the row blocks are ordered so one
  * graph's rows stay on one XCD (its gathered rows then hit that XCD's L2);
  * otherwise natural order.  row_order (optional, NULL = 0..n_rows-1) is the

@@ -885,7 +885,8 @@ static int launch_spmm_bf16_epi(const SpmmBfArgs& a, bool two, hipStream_t s) {
 
 int launch_spmm_bf16(const SpmmBfArgs& a, hipStream_t s) {
   if (a.R <= 0) return 0;
-  SND_CHECK_ARG(a.width % 8 == 0 && a.width <= 128 && a.ldh % 8 == 0, "spmm_bf16: width %% 8 <= 128, ldh %% 8");
+  SND_CHECK_ARG(a.width > 0 && a.width % 8 == 0 && a.width <= 128 && a.ldh % 8 == 0,
+                "spmm_bf16: 0 < width %% 8 <= 128, ldh %% 8");
   SND_CHECK_ARG((long long)a.R * a.ldh * 2 < (1ll << 31), "spmm_bf16: rows x ldh beyond the 2 GB buffer range");
   SND_CHECK_ARG(a.t_rows >= 0 && a.t_rows <= TRPG * TG, "spmm_bf16: tile_rows <= 128");
   SND_CHECK_ARG(a.t_rows == 0 || (a.t_rowid && a.t_trp && a.t_lcol && a.t_ucol && a.t_ustride >= 0 &&
