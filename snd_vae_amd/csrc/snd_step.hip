@@ -1500,11 +1500,14 @@ extern "C" int snd_plan_launch(const snd_plan_t* plan, const snd_batch_t* batch,
   char* ws = (char*)workspace;
   hipStream_t s = (hipStream_t)stream;
   const int L = p.dj;
-  if (!strncmp(kernel, "zzt_dense", 9)) {   // zzt_dense | zzt_dense_v<variant> (ZztArgs.variant)
+  if (!strncmp(kernel, "zzt_dense", 9)) {   // zzt_dense | zzt_dense_v<variant>[s<splits>] (ZztArgs)
     const ZztStage stg = zzt_stage(ws + p.buf("ZSTAGE"), p.B, p.N, L, p.c.dtype);
     const int variant = kernel[9] == '_' ? atoi(kernel + 11) : 0;   // zzt_dense_v<N>
     ZztArgs za{stg.jrow, stg.jt, p.N, zzt_npad(p.N), p.B, L, (float*)(ws + p.buf("DJD")),
                (double*)(ws + p.buf("PZZT")), stg.colpart, variant, (float*)(ws + p.buf("DJDX"))};
+    // zzt_dense_v<N>s<K>: K column splits instead of zzt_tsplit's choice (K = 1: every
+    // workgroup runs the whole tile range; launch_zzt_dense rejects more than DJDX holds)
+    if (const char* ks = strchr(kernel + 9, 's')) za.tsplit = atoi(ks + 1);
     return launch_zzt_dense(za, p.c.dtype, s);
   }
   if (!strcmp(kernel, "spmm_dxw1")) {   // A @ dP1 (plain SpMM, width h1)

@@ -1094,25 +1094,51 @@ __device__ __forceinline__ int zoa64(int row, int ch) {   // [128][64] bf16 imag
 }
 
 // MEAS (variant >= 256, measurement build; results wrong): phase skips, variant >> 8 --
-//   1 no epilogue, 4 no backward MFMAs, 16 the symmetric-tile proxy: odd tiles only DMA
+//   1 no epilogue, 4 no backward MFMAs, 2 the tile loop's skeleton (no epilogue and no
+//   MFMA at all: the DMAs, waits, barriers and LDS operand reads stay), 8 no tile DMA
+//   after each ring slot's first fill (the loop computes on stale tiles), 64 no tile at
+//   all (the prologue, the row corrections, the combine and the stores remain), 16 the
+//   symmetric-tile proxy: odd tiles only DMA
 //   and barrier, even tiles run their epilogue once and the backward MFMAs twice (what a
 //   J >= I tile kernel computes per logit block: forward 4 + epilogue + 2 x 4 backward
 //   MFMAs over half the blocks; DESIGN §5 "symmetric tiles, measured")
-template <bool STAG, bool MEAS>
-__global__ void __launch_bounds__(NTH9) __attribute__((amdgpu_waves_per_eu(4, 4)))
-zzt_dense_bf16_v9(ZztArgs a) {
+//
+// LOOP: the tile loop (A/B: ZztArgs.variant & 255 = 9 + LOOP, zzt_dense_v9 .. v12; the
+// arithmetic and its order are the same in all four, the results bitwise equal) --
+//   0  round 5's: -z_i rows in LDS, read again every tile; tile t + 1's DMA issued in
+//      tile t, a full vmcnt(0) drain and a barrier per tile; 3 slots
+//   1  the wave's four -z_i operands held in registers (loaded once from the row image;
+//      no LDS copy of the rows), the loop as 0
+//   2  1 + the DMA two tiles ahead: tile t + 2 goes into tile t - 1's slot, the tile ends
+//      on a counted vmcnt(2) (tile t + 1 landed, t + 2 in flight) and a barrier; 3 slots
+//   3  1 + two-tile stages on a 4-slot ring: the next stage's two fills are issued at the
+//      stage's start, both tiles run with no barrier between them, then one drain and
+//      one barrier per stage (half of 0's), every fill has two tile times to land
+constexpr int kZztLoops = 4;
+constexpr int kZztLoopShipped = 0;
+constexpr int kZztLoopVariant0 = 9;    // ZztArgs.variant & 255 of LOOP 0
+typedef int zv4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void zkeep(const bf16x8& v) {   // MEAS: an operand read stays without its MFMA
+  asm volatile("" ::"v"(__builtin_bit_cast(zv4i, v)));
+}
+
+template <bool STAG, bool MEAS, int LOOP>
+__device__ __forceinline__ void zzt_v9_body(const ZztArgs& a) {
+  static_assert(!STAG || LOOP == 0, "the stagger's deferred backward reads tile t - 1's slot");
   constexpr int DP = 64, NT = NTH9, NW = NT / 64;
   const int skip = MEAS ? __builtin_amdgcn_readfirstlane(a.variant >> 8) : 0;
   constexpr int KS = DP / 16;          // forward k-steps
   constexpr int CB = DP / 32;          // backward 32-column output blocks
   constexpr int IMG = TJ2 * DP * 2;    // one [128][64] bf16 image, 16 KB
-  __shared__ __attribute__((aligned(16))) char lds[3 * IMG + ROWS9 * DP * 2];   // ring, -z_i rows
+  constexpr int NS = LOOP == 3 ? 4 : 3;                          // ring slots
+  constexpr int BROWS = LOOP == 0 ? ROWS9 * DP * 2 : 0;          // the -z_i rows' LDS image
+  __shared__ __attribute__((aligned(16))) char lds[NS * IMG + BROWS];   // ring, -z_i rows
   __shared__ float colsum[DP];
   __shared__ float csred[NT / DP][DP];
   __shared__ float dsg[2][32];
   __shared__ double sl[NW];
   __shared__ unsigned sc[NW];
-  char* brows = lds + 3 * IMG;
+  char* brows = lds + NS * IMG;
   const unsigned lds0 = (unsigned)(uintptr_t)(zlptr_t)lds;
 
   const int wgs = a.ngraphs * zrb(a) * 2;
@@ -1127,7 +1153,8 @@ zzt_dense_bf16_v9(ZztArgs a) {
   const int i0 = __builtin_amdgcn_readfirstlane(r0 + 32 * rg);
   const int i_me = i0 + r;
   const int ntot = a.npad / TJ2;
-  const int t0 = sp * ntot / nsplit, t1 = (sp + 1) * ntot / nsplit;
+  const int t0 = sp * ntot / nsplit;
+  const int t1 = (MEAS && (skip & 64)) ? t0 : (sp + 1) * ntot / nsplit;   // 64: no tile at all
 
   // tile t -> ring slot b: 16 pieces of 1 KB (8 rows each), wave w issues pieces w and w + 8
   int dsrc[2];
@@ -1139,25 +1166,49 @@ zzt_dense_bf16_v9(ZztArgs a) {
     dsrc[k] = row * DP + 8 * ch;
   }
   auto dma = [&](int t, int b) {
+    if (MEAS && (skip & 8) && t >= t0 + NS) return;   // every slot filled once, then no DMA
 #pragma unroll
     for (int k = 0; k < 2; ++k)
       zdma16(Jg + (long long)t * TJ2 * DP + dsrc[k],
              __builtin_amdgcn_readfirstlane(lds0 + b * IMG + 1024 * (w + 8 * k)));
   };
 
-  // ---- prologue: tile t0 in flight; -z_i rows; column sums
+  // ---- prologue: tile t0 (LOOP >= 2: and t0 + 1) in flight; -z_i rows; column sums
   dma(t0, 0);
-  for (int idx = tid; idx < ROWS9 * (DP / 8); idx += NT) {
-    const int row = idx >> 3, ch = idx & 7;
-    const uint4 u = *reinterpret_cast<const uint4*>(Jg + (long long)(r0 + row) * DP + ch * 8);
-    *reinterpret_cast<uint4*>(brows + zoa64(row, ch)) =
-        make_uint4(u.x ^ 0x80008000u, u.y ^ 0x80008000u, u.z ^ 0x80008000u, u.w ^ 0x80008000u);
+  if (LOOP >= 2 && t0 + 1 < t1) dma(t0 + 1, 1);
+  const int ja = 32 * cb + r, ia = 32 * rg + r;
+  bf16x8 bz[KS];   // LOOP >= 1: the forward B operands, k-step s = -z_i chunk 2 s + h
+  if constexpr (LOOP == 0) {
+    for (int idx = tid; idx < ROWS9 * (DP / 8); idx += NT) {
+      const int row = idx >> 3, ch = idx & 7;
+      const uint4 u = *reinterpret_cast<const uint4*>(Jg + (long long)(r0 + row) * DP + ch * 8);
+      *reinterpret_cast<uint4*>(brows + zoa64(row, ch)) =
+          make_uint4(u.x ^ 0x80008000u, u.y ^ 0x80008000u, u.z ^ 0x80008000u, u.w ^ 0x80008000u);
+    }
+  } else {
+    const uint4* src = reinterpret_cast<const uint4*>(Jg + (long long)(r0 + ia) * DP + 8 * h);
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const uint4 u = src[2 * s];
+      bz[s] = __builtin_bit_cast(bf16x8, make_uint4(u.x ^ 0x80008000u, u.y ^ 0x80008000u,
+                                                    u.z ^ 0x80008000u, u.w ^ 0x80008000u));
+    }
   }
   {
     const int nrb = a.npad / 64;
     const int k = tid % DP, grp = tid / DP;
     float s = 0.f;
-    for (int p = grp; p < nrb; p += NT / DP) s += a.colpart[((long long)g * nrb + p) * DP + k];
+    // eight partials in flight at a time, added in the same order (one load per loop trip
+    // made every trip a dependent L2 round trip: 8 in a row at N = 4096)
+    for (int p0 = grp; p0 < nrb; p0 += 8 * (NT / DP)) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)   // clamped, so the load is unconditional
+        v[j] = a.colpart[((long long)g * nrb + min(p0 + j * (NT / DP), nrb - 1)) * DP + k];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (p0 + j * (NT / DP) < nrb) s += v[j];
+    }
     csred[grp][k] = s;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1174,9 +1225,14 @@ zzt_dense_bf16_v9(ZztArgs a) {
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[q][v] = 0.f;
   // forward operand bases (k-step s: base[s & 1] + 512 (s >> 1))
-  const int ja = 32 * cb + r, ia = 32 * rg + r;
   const int fa0 = zoa64(ja, h), fa1 = zoa64(ja, 2 + h);
-  const int fb0 = zoa64(ia, h), fb1 = zoa64(ia, 2 + h);
+  const int fb0 = zoa64(ia, h), fb1 = zoa64(ia, 2 + h);   // LOOP 0
+  auto brow = [&](int s) {
+    if constexpr (LOOP == 0)
+      return *reinterpret_cast<const bf16x8*>(brows + ((s & 1) ? fb1 : fb0) + 512 * (s >> 1));
+    else
+      return bz[s];
+  };
   // backward transposed-read bases (v7's, 8-row groups of 1 KB): lane 4 qq + pp of group
   // gq supplies row 32 cb + 16 s + 8 t + 4 (gq >> 1) + qq, columns 32 q + 16 (gq & 1) + 4 pp
   const int gq = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
@@ -1191,7 +1247,8 @@ zzt_dense_bf16_v9(ZztArgs a) {
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       const bf16x8 av = *reinterpret_cast<const bf16x8*>(T + ((s & 1) ? fa1 : fa0) + 512 * (s >> 1));
-      const bf16x8 bv = *reinterpret_cast<const bf16x8*>(brows + ((s & 1) ? fb1 : fb0) + 512 * (s >> 1));
+      const bf16x8 bv = brow(s);
+      if (MEAS && (skip & 2)) { zkeep(av); zkeep(bv); continue; }
       X = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, X, 0, 0, 0);
     }
     return X;
@@ -1201,7 +1258,7 @@ zzt_dense_bf16_v9(ZztArgs a) {
   unsigned lcnt = 0;
   bool ovf = false;   // sticky per wave, as v4
   auto epi = [&](const f32x16& Y, bf16x8 (&sA)[2]) {   // v4's epilogue, y = -x
-    if (MEAS && (skip & 1)) {
+    if (MEAS && (skip & 3)) {
 #pragma unroll
       for (int v = 0; v < 16; ++v) sA[v >> 3][v & 7] = (__bf16)Y[v];
       return;
@@ -1244,6 +1301,7 @@ zzt_dense_bf16_v9(ZztArgs a) {
 #pragma unroll
       for (int q = 0; q < CB; ++q) {
         const bf16x8 bv = ztr_pair(T + tb0 + 2048 * s + 512 * q + 8 * rep, T + tb1 + 2048 * s + 512 * q + 8 * rep);
+        if (MEAS && (skip & 2)) { zkeep(bv); continue; }
         acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sA[s], bv, acc[q], 0, 0, 0);
       }
   };
@@ -1286,7 +1344,73 @@ zzt_dense_bf16_v9(ZztArgs a) {
       lacc = 0.f;
     }
   };
-  if (STAG && !MEAS && (cb & 1)) {
+  // one whole tile out of slot b
+  auto whole = [&](int b) {
+    const f32x16 Y = fwd(b);
+    bf16x8 sA[2];
+    epi(Y, sA);
+    bwd(b, sA);
+  };
+  // the end of a tile (LOOP 2) or stage (LOOP 3): this wave's fills landed, but for its
+  // last two pieces where a later tile is in flight; its LDS reads done; then the barrier
+  // (raw: the fills in flight are not drained)
+  auto tile_end = [&](bool two_in_flight) {
+    if (two_in_flight) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+  // LOOP 2: tiles t and t + 1 issued before tile t starts; t + 2 goes into t - 1's slot,
+  // which every wave left at the barrier that ended t - 1
+  auto run_ahead2 = [&]() {
+    auto tile = [&](int t, auto cc) {
+      constexpr int CUR = decltype(cc)::value;
+      const bool more = t + 2 < t1;
+      if (more) dma(t + 2, (CUR + 2) % 3);
+      whole(CUR);
+      tile_end(more);   // tile t + 1 landed
+    };
+    for (int t = t0; t < t1; t += 3) {
+      tile(t, std::integral_constant<int, 0>{});
+      if (t + 1 < t1) tile(t + 1, std::integral_constant<int, 1>{});
+      if (t + 2 < t1) tile(t + 2, std::integral_constant<int, 2>{});
+      ltot += (double)lacc;
+      lacc = 0.f;
+    }
+  };
+  // LOOP 3: the stage of tiles t, t + 1 in slots S, S + 1; the next stage's fills go into
+  // the other pair, which every wave left at the barrier that ended the stage before.
+  // lacc is folded every third tile, as the one-tile loops do (the same sums, bitwise)
+  auto run_stages = [&]() {
+    int ph = 0;
+    auto one = [&](int b) {
+      whole(b);
+      if (++ph == 3) {
+        ltot += (double)lacc;
+        lacc = 0.f;
+        ph = 0;
+      }
+    };
+    auto stage = [&](int t, auto cc) {
+      constexpr int S = decltype(cc)::value;
+      if (t + 2 < t1) dma(t + 2, S ^ 2);
+      if (t + 3 < t1) dma(t + 3, (S ^ 2) + 1);
+      one(S);
+      if (t + 1 < t1) one(S + 1);
+      tile_end(false);   // the next stage landed
+    };
+    for (int t = t0; t < t1; t += 4) {
+      stage(t, std::integral_constant<int, 0>{});
+      if (t + 2 < t1) stage(t + 2, std::integral_constant<int, 2>{});
+    }
+    ltot += (double)lacc;
+    lacc = 0.f;
+  };
+  if constexpr (LOOP == 2) {
+    run_ahead2();
+  } else if constexpr (LOOP == 3) {
+    run_stages();
+  } else if (STAG && !MEAS && (cb & 1)) {
     __builtin_amdgcn_s_setprio(1);
     run(std::true_type{});
     __builtin_amdgcn_s_setprio(0);
@@ -1298,7 +1422,7 @@ zzt_dense_bf16_v9(ZztArgs a) {
   float xd = 0.f, xs = 0.f;
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
-    const bf16x8 bv = *reinterpret_cast<const bf16x8*>(brows + ((s & 1) ? fb1 : fb0) + 512 * (s >> 1));
+    const bf16x8 bv = brow(s);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float bb = (float)bv[e];
@@ -1324,7 +1448,7 @@ zzt_dense_bf16_v9(ZztArgs a) {
   }
 
   // ---- combine the four column blocks' partial dJ (fixed order) through the ring's
-  // 48 KB; the diagonal term subtracted with the scaled z_i the backward products used,
+  // first 48 KB; the diagonal term subtracted with the scaled z_i the backward products used,
   // then the sqrt(log2 e) scale removed
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -1332,12 +1456,22 @@ zzt_dense_bf16_v9(ZztArgs a) {
   float* dst = (sp == 0 ? a.dJd : a.dJd_extra + (long long)(sp - 1) * a.ngraphs * a.n * a.d) +
                (long long)g * a.n * a.d;
   const __bf16* zi = Jg + (long long)(r0 + 32 * rg) * DP;
+  // the diagonal term's z_i, all 32 loaded before the barrier (rows of the padded image,
+  // in bounds for every lane): loaded inside the guarded store below, each element waited
+  // for its own load and for the store before it, 32 memory round trips in a row
+  float zd[CB][16];
   if (cb > 0) {
 #pragma unroll
     for (int q = 0; q < CB; ++q)
 #pragma unroll
       for (int v = 0; v < 16; ++v)
         red[(((cb - 1) * 2 + rg) * (CB * 16) + q * 16 + v) * 64 + lane] = acc[q][v];
+  } else {
+#pragma unroll
+    for (int q = 0; q < CB; ++q)
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        zd[q][v] = (float)zi[((v & 3) + 8 * (v >> 2) + 4 * h) * DP + 32 * q + r];
   }
   __syncthreads();
   if (cb == 0) {
@@ -1352,7 +1486,7 @@ zzt_dense_bf16_v9(ZztArgs a) {
         const int il = (v & 3) + 8 * (v >> 2) + 4 * h;   // D row within the row group
         const int i = i0 + il;
         if (i < a.n && c < a.d)
-          dst[(long long)i * a.d + c] = (o - dsg[rg][il] * (float)zi[il * DP + c]) * kInvSqrtLog2e;
+          dst[(long long)i * a.d + c] = (o - dsg[rg][il] * zd[q][v]) * kInvSqrtLog2e;
       }
     }
   }
@@ -1370,6 +1504,20 @@ zzt_dense_bf16_v9(ZztArgs a) {
     a.part[2 * blockIdx.x] = tl * (double)kLn2;
     a.part[2 * blockIdx.x + 1] = tc;
   }
+}
+
+// the shipped kernel (the stagger build keeps loop 0: its deferred backward still reads
+// tile t - 1's slot, so it cannot prefetch two tiles ahead)
+template <bool STAG, bool MEAS>
+__global__ void __launch_bounds__(NTH9) __attribute__((amdgpu_waves_per_eu(4, 4)))
+zzt_dense_bf16_v9(ZztArgs a) {
+  zzt_v9_body<STAG, MEAS, STAG ? 0 : kZztLoopShipped>(a);
+}
+// one named tile loop (A/B, ZztArgs.variant & 255 = 9 + LOOP)
+template <int LOOP, bool MEAS>
+__global__ void __launch_bounds__(NTH9) __attribute__((amdgpu_waves_per_eu(4, 4)))
+zzt_dense_bf16_v9_loop(ZztArgs a) {
+  zzt_v9_body<false, MEAS, LOOP>(a);
 }
 
 // dJd += sum of the column-split partials (fixed order)
@@ -1484,7 +1632,11 @@ int launch_zzt_dense(const ZztArgs& a, int dtype, hipStream_t s, bool defer_spli
   SND_CHECK_ARG(a.rb0 >= 0 && a.nrb >= 0 && a.rb0 + zrb(a) <= a.npad / ROWS,
                 "zzt_dense: row blocks [%d, %d) outside the %d of the graph", a.rb0, a.rb0 + zrb(a),
                 a.npad / ROWS);
-  const int ts = (dtype == SND_BF16 && a.variant == 0)
+  // v9's named tile loops (variant & 255 = 9 .. 12): the default kernel with another loop
+  const int loop9 = (a.variant & 255) - kZztLoopVariant0;
+  const bool v9 = dtype == SND_BF16 && dp == 64 && SND_ZZT_V9;
+  const bool v9loop = v9 && loop9 >= 0 && loop9 < kZztLoops;
+  const int ts = (dtype == SND_BF16 && (a.variant == 0 || (v9loop && a.variant < 256)))
                      ? (a.tsplit > 0 ? a.tsplit : zzt_tsplit_blocks(a.ngraphs * zrb(a), a.n, dtype)) : 1;
   SND_CHECK_ARG(ts <= std::max(1, zzt_tsplit_blocks(a.ngraphs * zrb(a), a.n, dtype)),
                 "zzt_dense: %d column splits > the %d the scratch is sized for", ts,
@@ -1496,7 +1648,23 @@ int launch_zzt_dense(const ZztArgs& a, int dtype, hipStream_t s, bool defer_spli
     if (dp == 32) hipLaunchKernelGGL((zzt_dense_bf16<32>), grid, dim3(NTH), 0, s, a);
     else if (dp == 64) hipLaunchKernelGGL((zzt_dense_bf16<64>), grid, dim3(NTH), 0, s, a);
     else hipLaunchKernelGGL((zzt_dense_bf16<128>), grid, dim3(NTH), 0, s, a);
-  } else if (dtype == SND_BF16 && dp == 64 && SND_ZZT_V9 && (a.variant == 0 || a.variant >= 256)) {   // v9
+  } else if (v9loop) {                                // v9 with a named tile loop (A/B)
+    const dim3 g9(grid.x * 2);
+#define SND_V9_LOOP(LP)                                                                      \
+  case LP:                                                                                   \
+    if (a.variant >= 256)                                                                    \
+      hipLaunchKernelGGL((zzt_dense_bf16_v9_loop<LP, true>), g9, dim3(NTH9), 0, s, a);       \
+    else                                                                                     \
+      hipLaunchKernelGGL((zzt_dense_bf16_v9_loop<LP, false>), g9, dim3(NTH9), 0, s, a);      \
+    break
+    switch (loop9) {
+      SND_V9_LOOP(0);
+      SND_V9_LOOP(1);
+      SND_V9_LOOP(2);
+      SND_V9_LOOP(3);
+    }
+#undef SND_V9_LOOP
+  } else if (v9 && (a.variant == 0 || a.variant >= 256)) {   // v9
     const dim3 g9(grid.x * 2);
     if (a.variant >= 256) hipLaunchKernelGGL((zzt_dense_bf16_v9<false, true>), g9, dim3(NTH9), 0, s, a);
     else if (SND_ZZT_V9 == 2) hipLaunchKernelGGL((zzt_dense_bf16_v9<true, false>), g9, dim3(NTH9), 0, s, a);

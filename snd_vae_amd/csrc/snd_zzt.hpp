@@ -12,7 +12,10 @@ struct ZztArgs {
   const float* colpart;  // [B][npad/64][DP] column sums of jrow (bf16 values), per 64 rows
   int variant;           // bf16 kernel: 0 = default (v4 for d <= 64, v7 for d = 128), 1 = v1
                          // (the bench's previous variant); >= 256 the measurement build of the
-                         // default (phase-skip / stamp bits variant >> 8, tools/zzt_stamps.py)
+                         // default (phase-skip / stamp bits variant >> 8, tools/zzt_stamps.py);
+                         // d = 64 (v9): variant & 255 = 9 .. 12 names one of its tile loops
+                         // (9 round 5's, 10 -z_i in registers, 11 + DMA two tiles ahead,
+                         // 12 + two-tile stages), column splits as the default
   float* dJd_extra;      // v3 column splits 1.. (zzt_tsplit > 1): [(tsplit-1)][B*n][d] scratch
   int rb0 = 0;           // first 128-row block of the launch (row-sharded zz^T, snd_zzt_ce_rows)
   int nrb = 0;           // row blocks of the launch; 0 = every row block
