@@ -130,29 +130,55 @@ __global__ void __launch_bounds__(RCT) rowconv_kernel(RcArgs a) {
       glds16(g + ((long long)(t * np + nbase) * kp * 2) + (jj << 10), reinterpret_cast<char*>(ws) + (j << 10));
     }
   }
-  // ---- per-column parameters
+  // ---- CSR bounds of the gathered row (RC_ENC0 with a CSR: T = 1, one pass of the row
+  // loop), requested with the column parameters so that both share one round trip
+  int grp0 = 0, grp1 = 0;
+  if constexpr (EPI == RC_ENC0 && NBH <= 2) {
+    if (a.g_rowptr) {
+      const int grc = min(r0 + (tid >> 3), a.R - 1);
+      grp0 = a.g_rowptr[grc];
+      grp1 = a.g_rowptr[grc + 1];
+    }
+  }
+  // ---- per-column parameters: one group of unconditional loads.  A column without the
+  // parameter reads the zero buffer (address select, no branch: a load inside a
+  // per-parameter branch was waited for on its own, seven round trips in a row)
   if (tid < nloc) {
     const int nl = tid, n = nbase + tid;
     const bool cv = n < a.N && a.cols.valid(n) && !(kdbg(a.dbg) & 16);
     const bool pa = n < a.cols.a;
     const int ia = pa ? n : a.cols.logical(n), ib = n - a.cols.offb;
+    const float* zf = reinterpret_cast<const float*>(a.zero);
     auto par = [&](const float* A, const float* Bv) {
-      return !cv || !A ? 0.f : (pa || !Bv ? A[ia] : Bv[ib]);
+      return !cv || !A ? zf : (pa || !Bv ? A + ia : Bv + ib);
     };
-    colp[0][nl] = par(a.bias, a.bias_b);
-    colp[1][nl] = par(a.gamma, a.gamma_b) * kBnC;
-    colp[2][nl] = par(a.beta, a.beta_b);
+    const float* src[7] = {par(a.bias, a.bias_b), par(a.gamma, a.gamma_b), par(a.beta, a.beta_b), zf, zf, zf, zf};
     if constexpr (EPI == RC_ENC1) {
-      colp[3][nl] = (cv && n < a.h) ? a.g2[n] * kBnC : 0.f;
-      colp[4][nl] = (cv && n < a.h) ? a.b2[n] : 0.f;
+      src[3] = (cv && n < a.h) ? a.g2 + n : zf;
+      src[4] = (cv && n < a.h) ? a.b2 + n : zf;
     }
     if constexpr (EPI == RC_ENC0) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) colp[3 + k][nl] = (cv && k < a.f) ? a.w0[k * a.N + n] : 0.f;
+      for (int k = 0; k < 4; ++k) src[3 + k] = (cv && k < a.f) ? a.w0 + (k * a.N + n) : zf;
     }
     if constexpr (EPI == RC_LIN || EPI == RC_FWD) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) colp[3 + k][nl] = (cv && k < a.ktail) ? a.wtail[k * a.ldwt + n] : 0.f;
+      for (int k = 0; k < 4; ++k) src[3 + k] = (cv && k < a.ktail) ? a.wtail + (k * a.ldwt + n) : zf;
+    }
+    constexpr int NP = EPI == RC_ENC1 ? 5 : (EPI == RC_ENC0 || EPI == RC_LIN || EPI == RC_FWD ? 7 : 3);
+    float pv[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) pv[k] = *src[k];
+    colp[0][nl] = pv[0];
+    colp[1][nl] = pv[1] * kBnC;
+    colp[2][nl] = pv[2];
+    if constexpr (EPI == RC_ENC1) {
+      colp[3][nl] = pv[3] * kBnC;
+      colp[4][nl] = pv[4];
+    }
+    if constexpr (NP == 7) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) colp[3 + k][nl] = pv[3 + k];
     }
   }
 
@@ -190,7 +216,7 @@ __global__ void __launch_bounds__(RCT) rowconv_kernel(RcArgs a) {
         float acc8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (gr < rend) {
           const __amdgpu_buffer_rsrc_t rsx = rows_rsrc(a.x, (long long)a.R * a.ldx * 2);
-          gather_rows16<1>(a.g_colidx, a.g_rowptr[gr], a.g_rowptr[gr + 1], rsx, 2u * a.ldx, sub,
+          gather_rows16<1>(a.g_colidx, grp0, grp1, rsx, 2u * a.ldx, sub,
                            [&](int, const u32x4 (&v)[1], bool) { acc8v(acc8, v[0]); });
         }
         const uint4 o = to_bf16x8(acc8);
@@ -247,9 +273,13 @@ __global__ void __launch_bounds__(RCT) rowconv_kernel(RcArgs a) {
     }
     float ax[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (EPI == RC_ENC0) {
-      if (rv)
+      if (rv && a.f > 0) {   // one group of unconditional loads (clamped column), select after
+        float t[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) if (k < a.f) ax[k] = a.p[(long long)r * a.ldp + k];
+        for (int k = 0; k < 4; ++k) t[k] = a.p[(long long)r * a.ldp + min(k, a.f - 1)];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ax[k] = k < a.f ? t[k] : 0.f;
+      }
     }
     if constexpr (EPI == RC_LIN || EPI == RC_FWD) {   // the x columns past the image
       if (rv && a.ktail > 0) {

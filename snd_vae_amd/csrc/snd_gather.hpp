@@ -35,20 +35,31 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_rsrc(const void* base, lo
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
 }
 
-// Per round the row's next 16 neighbour ids are loaded one or two per lane and
+// Per round the row's next 16 neighbour ids are taken one or two per lane and
 // broadcast inside the 8-lane group, and all 16 neighbour chunks are requested
-// before any is consumed: a row of degree <= 16 costs one rowptr -> colidx ->
-// gather latency chain.  The gathers are buffer loads with a 32-bit offset (one
-// mad per neighbour, no 64-bit address arithmetic); a missing neighbour (past the
-// row end, id -1) wraps its offset past the descriptor's range, so the hardware
-// returns zeros with no select.  fn(u, v, valid) consumes neighbour u of the round
-// in order; cross-lane work inside fn stays uniform over the row's 8 lanes.
+// before any is consumed.  The ids of round k + 1 are requested before round k's
+// rows, so the chain of dependent round trips is rowptr -> ids -> rows -> rows ...
+// and not ids -> rows -> ids -> rows: a row of degree <= 32 pays one id latency.
+// The id loads are unconditional (index clamped to the row's last entry, never past
+// colidx[e - 1]; the select to -1 follows the load), so nothing waits inside a branch.
+// The gathers are buffer loads with a 32-bit offset (one mad per neighbour, no 64-bit
+// address arithmetic); a missing neighbour (past the row end, id -1) wraps its offset
+// past the descriptor's range, so the hardware returns zeros with no select.
+// fn(u, v, valid) consumes neighbour u of the round in order; cross-lane work inside
+// fn stays uniform over the row's 8 lanes.
 template <int NQ, typename Fn>
 __device__ __forceinline__ void gather_rows16(const int* colidx, int s, int e, __amdgpu_buffer_rsrc_t rs,
                                               unsigned row_bytes, int sub, Fn&& fn) {
+  if (s >= e) return;
+  const int last = e - 1;
+  int n0 = colidx[min(s + sub, last)], n1 = colidx[min(s + 8 + sub, last)];
   for (int k0 = s; k0 < e; k0 += 16) {
-    const int id0 = k0 + sub < e ? colidx[k0 + sub] : -1;
-    const int id1 = k0 + 8 + sub < e ? colidx[k0 + 8 + sub] : -1;
+    const int id0 = k0 + sub < e ? n0 : -1;
+    const int id1 = k0 + 8 + sub < e ? n1 : -1;
+    // the next round's ids: in flight under this round's rows (clamped: a round past
+    // the row end re-reads the last entry and is never used)
+    n0 = colidx[min(k0 + 16 + sub, last)];
+    n1 = colidx[min(k0 + 24 + sub, last)];
     int c[16];
     c[0] = bcast8<0>(id0); c[1] = bcast8<1>(id0); c[2] = bcast8<2>(id0); c[3] = bcast8<3>(id0);
     c[4] = bcast8<4>(id0); c[5] = bcast8<5>(id0); c[6] = bcast8<6>(id0); c[7] = bcast8<7>(id0);

@@ -9,7 +9,7 @@
 //      and G = BNe([BN1(lrelu(P1)) | X]) leave for the backward pass, G also lands in
 //      LDS as the [row][k] image the row engine would have staged from HBM;
 //   2. h = G Wh + bh (model.py:113) on v_mfma_f32_16x16x32_bf16 from that image and
-//      the packed weight image (LDS-DMA'd during the gather), bf16 h to HBM (the Wms
+//      the packed weight image (LDS-DMA'd with the prologue's loads), bf16 h to HBM (the Wms
 //      weight gradient reads it) and to LDS;
 //   3. [mu | s] = h Wms + bms (model.py:114-115), fp32 to HBM; the s half crosses to
 //      the mu waves through LDS;
@@ -61,7 +61,7 @@ struct FwdLay {
     sx_end = 2 * HR * (L + 4) * 4;
   }
 };
-constexpr int kHeadStaticLds = 2 * 128 * 4 + 2 * HWMAX * 8;
+constexpr int kHeadStaticLds = 2 * 128 * 4 + 4 * 80 * 4 + 2 * HWMAX * 8;
 constexpr int kHeadDynLds = 160 * 1024 - kHeadStaticLds - 512;
 
 // LDS-DMA a packed [np][kp] bf16 weight image (whole 1 KB pieces)
@@ -102,11 +102,23 @@ __device__ __forceinline__ bf16x4* img_at4(__bf16* img, int row, int n0, int kp)
   return reinterpret_cast<bf16x4*>(img + row * kp + (((n0 >> 3) ^ hswz(row, kp)) << 3) + (n0 & 4));
 }
 
+// The F fp32 features of node c, zero-extended to N: one load of F dwords (the rows are
+// only 4-byte aligned; a load per element costs the address path F times the lines, and
+// that path is what the front's neighbour gather saturates)
+template <int F, int N>
+__device__ __forceinline__ void feat_row(const float* x, int ldx, long long c, float (&v)[N]) {
+  struct __attribute__((packed, aligned(4))) Row { float f[F]; };
+  const Row t = *reinterpret_cast<const Row*>(x + c * ldx);
+#pragma unroll
+  for (int j = 0; j < N; ++j) v[j] = j < F ? t.f[j < F ? j : 0] : 0.f;
+}
+
 template <int HR, int NB1, int NB2>
 __global__ void __launch_bounds__(HR * 8) head_fwd_kernel(HeadFwdArgs a) {
   constexpr int HT = HR * 8, HW = HT / 64, NRB = HR / 16;   // threads, waves, 16-row blocks
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float cb1[128], cb2[128];   // bh, bms per physical column
+  __shared__ float cbn[4][80];           // g1, b1 (h1 columns), ge, be (h1 + f columns)
   __shared__ double klw[2 * HWMAX];
   const FwdLay lay(HR, a.kp1, a.np1, a.kp2, a.np2, a.L);
   __bf16* w2s = reinterpret_cast<__bf16*>(smem + lay.w2);
@@ -132,50 +144,76 @@ __global__ void __launch_bounds__(HR * 8) head_fwd_kernel(HeadFwdArgs a) {
   const int lr0 = lt * HR;                          // first row of the tile in its graph
   const long long gr0 = (long long)gi * a.npg;      // the graph's first global row
 
-  // ---- weight images in flight during the gather; biases; zero h image (pad columns)
-  stage_img(a.wh_img, a.np1 * a.kp1 * 2, reinterpret_cast<char*>(w1s), HW);
-  stage_img(a.wms_img, a.np2 * a.kp2 * 2, reinterpret_cast<char*>(w2s), HW);
-  for (int i = tid; i < 128; i += HT) {
-    cb1[i] = i < a.gh ? a.bh[i] : 0.f;
-    cb2[i] = i < 2 * L ? a.bms[i] : 0.f;
-  }
+  // ---- prologue: one group of independent requests, one wait.  The h image's pad
+  // columns are zeroed first (an LDS write behind an LDS-DMA is made to wait for it), then
+  // every small operand (biases, BN column parameters, the row's CSR bounds and its own
+  // features: unconditional, index clamped, select after the load) and the two weight
+  // images go out together.  A small load behind a DMA cannot be waited for without
+  // draining the DMA (the counter retires in order), so the images land with this group
+  // and not "during the gather"; the gather then starts with its operands in registers.
   for (int i = tid; i < HR * a.kp2 / 8; i += HT) reinterpret_cast<uint4*>(hs)[i] = make_uint4(0u, 0u, 0u, 0u);
-
-  // ---- 1. P1 = A XW1 for row rs (8 lanes), GraphConvolution 1 epilogue
   const int rs = tid >> 3, sub = tid & 7;
   const int lr = lr0 + rs;
   const bool rv = lr < a.npg;
   const long long r = gr0 + lr;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (rv && !(kdbg(a.dbg) & 1)) {
-    const __amdgpu_buffer_rsrc_t rsd = rows_rsrc(a.xw1, (long long)a.R * a.h1 * 2);
-    gather_rows16<1>(a.colidx, a.rowptr[r], a.rowptr[r + 1], rsd, 2u * a.h1, sub,
-                     [&](int, const u32x4 (&v)[1], bool) { acc8v(acc, v[0]); });
-  }
+  const long long rc = gr0 + min(lr, a.npg - 1);
   const int nch = a.h1 >> 3, kc1 = a.kp1 >> 3;
-  uint4 gdat = make_uint4(0u, 0u, 0u, 0u), gxv = make_uint4(0u, 0u, 0u, 0u);
-  if (sub < nch) {
-    float gv[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = 8 * sub + j;
-      const float b1 = lrelu(acc[j]) * (a.g1[c] * kBnC) + a.b1[c];     // H2[:, :h1]
-      gv[j] = b1 * (a.ge[c] * kBnC) + a.be[c];                          // encoder_g BN
-    }
-    gdat = to_bf16x8(gv);
-  }
   // the concat-X chunk (model.py:109) is chunk nch: lane nch's first or lane nch-8's second
   const int xo = (sub == nch) ? 0 : (sub + 8 == nch ? 1 : -1);
+  const int pc = tid & 127;
+  const float bhv = a.bh[min(pc, a.gh - 1)], bmsv = a.bms[min(pc, 2 * L - 1)];
+  const int bc1 = min(tid, a.h1 - 1), bce = min(tid, a.h1 + a.f - 1);
+  const float g1v = a.g1[bc1], b1v = a.b1[bc1], gev = a.ge[bce], bev = a.be[bce];
+  const int rp0 = a.rowptr[rc], rp1 = a.rowptr[rc + 1];
+  float xown[8];
+  switch (a.f) {
+    case 1: feat_row<1, 8>(a.x, a.ldx, rc, xown); break;
+    case 2: feat_row<2, 8>(a.x, a.ldx, rc, xown); break;
+    case 3: feat_row<3, 8>(a.x, a.ldx, rc, xown); break;
+    case 4: feat_row<4, 8>(a.x, a.ldx, rc, xown); break;
+    case 5: feat_row<5, 8>(a.x, a.ldx, rc, xown); break;
+    case 6: feat_row<6, 8>(a.x, a.ldx, rc, xown); break;
+    case 7: feat_row<7, 8>(a.x, a.ldx, rc, xown); break;
+    default: feat_row<8, 8>(a.x, a.ldx, rc, xown); break;
+  }
+  stage_img(a.wh_img, a.np1 * a.kp1 * 2, reinterpret_cast<char*>(w1s), HW);
+  stage_img(a.wms_img, a.np2 * a.kp2 * 2, reinterpret_cast<char*>(w2s), HW);
+  if (tid < 128) {
+    cb1[tid] = tid < a.gh ? bhv : 0.f;
+    cb2[tid] = tid < 2 * L ? bmsv : 0.f;
+  }
+  if (tid < 80) { cbn[0][tid] = g1v; cbn[1][tid] = b1v; cbn[2][tid] = gev; cbn[3][tid] = bev; }
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the group, weight images included
+  __syncthreads();
+  uint4 gdat = make_uint4(0u, 0u, 0u, 0u), gxv = make_uint4(0u, 0u, 0u, 0u);
   if (xo >= 0 && rv) {
     float gv[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = a.h1 + j;
-      gv[j] = j < a.f ? a.x[r * a.ldx + j] * (a.ge[c] * kBnC) + a.be[c] : 0.f;
+      gv[j] = j < a.f ? xown[j] * (cbn[2][c] * kBnC) + cbn[3][c] : 0.f;
     }
     gxv = to_bf16x8(gv);
+  }
+
+  // ---- 1. P1 = A XW1 for row rs (8 lanes), GraphConvolution 1 epilogue
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  if (rv && !(kdbg(a.dbg) & 1)) {
+    const __amdgpu_buffer_rsrc_t rsd = rows_rsrc(a.xw1, (long long)a.R * a.h1 * 2);
+    gather_rows16<1>(a.colidx, rp0, rp1, rsd, 2u * a.h1, sub,
+                     [&](int, const u32x4 (&v)[1], bool) { acc8v(acc, v[0]); });
+  }
+  if (sub < nch) {
+    float gv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = 8 * sub + j;
+      const float b1 = lrelu(acc[j]) * (cbn[0][c] * kBnC) + cbn[1][c];   // H2[:, :h1]
+      gv[j] = b1 * (cbn[2][c] * kBnC) + cbn[3][c];                        // encoder_g BN
+    }
+    gdat = to_bf16x8(gv);
   }
   {
     // chunk sub: data, the X chunk or zeros; chunk sub + 8: the X chunk or zeros
@@ -187,8 +225,7 @@ __global__ void __launch_bounds__(HR * 8) head_fwd_kernel(HeadFwdArgs a) {
     if (sub < kc1) *reinterpret_cast<uint4*>(gs + rs * a.kp1 + ((sub ^ hswz(rs, a.kp1)) << 3)) = v0;
     if (sub + 8 < kc1) *reinterpret_cast<uint4*>(gs + rs * a.kp1 + (((sub + 8) ^ hswz(rs, a.kp1)) << 3)) = v1;
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): weight images landed (gathers consumed)
-  __syncthreads();
+  __syncthreads();   // the G image
   // P1 and G leave for the backward pass while the heads run
   if (rv && !(kdbg(a.dbg) & 8)) {
     if (sub < nch) {
@@ -394,16 +431,13 @@ __global__ void __launch_bounds__(HR * 8) head_bwd_kernel(HeadBwdArgs a) {
   }
   const int r0 = t * HR;
 
-  stage_img(a.wmsb_img, a.np1 * a.kp1 * 2, reinterpret_cast<char*>(w1s), HW);
-  stage_img(a.whb_img, a.np2 * a.kp2 * 2, reinterpret_cast<char*>(w2s), HW);
-  // the dh image's columns [gh, kp2) are the zero k-padding the row engine stages
+  // the dh image's columns [gh, kp2) are the zero k-padding the row engine stages; zeroed
+  // before the weight images are requested (an LDS write behind an LDS-DMA waits for it)
   for (int i = tid; i < HR * a.kp2 / 8; i += HT) reinterpret_cast<uint4*>(dh_img)[i] = make_uint4(0u, 0u, 0u, 0u);
-  for (int n = tid; n < 128; n += HT) {   // rowconv RC_ENC1 column parameters
-    const bool cv = n < a.W;
-    colp[1][n] = cv ? a.ge[n] * kBnC : 0.f;
-    colp[3][n] = (cv && n < a.h1) ? a.g1[n] * kBnC : 0.f;
-    colp[4][n] = (cv && n < a.h1) ? a.b1[n] : 0.f;
-  }
+  // rowconv RC_ENC1 column parameters: unconditional loads (clamped index, select after),
+  // requested with the row's own operands below and ahead of the weight images
+  const int pn = min(tid, 127);
+  const float pge = a.ge[min(pn, a.W - 1)], pg1 = a.g1[min(pn, a.h1 - 1)], pb1 = a.b1[min(pn, a.h1 - 1)];
 
   // ---- 1. per-edge terms of row rs (edge_bf16_kernel) + reparameterisation backward
   {
@@ -425,14 +459,24 @@ __global__ void __launch_bounds__(HR * 8) head_bwd_kernel(HeadBwdArgs a) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) ej[q][j] = 0.f;
     }
+    const int rc = min(r, a.R - 1);
+    const int rp0 = a.rowptr[rc], rp1 = a.rowptr[rc + 1];
     if (rv)
 #pragma unroll
       for (int q = 0; q < NQ; ++q)
         if (qv[q]) zi[q] = *reinterpret_cast<const u32x4*>(a.zb + (long long)r * L + 64 * q + 8 * sub);
+    stage_img(a.wmsb_img, a.np1 * a.kp1 * 2, reinterpret_cast<char*>(w1s), HW);
+    stage_img(a.whb_img, a.np2 * a.kp2 * 2, reinterpret_cast<char*>(w2s), HW);
+    if (tid < 128) {
+      const bool cv = tid < a.W;
+      colp[1][tid] = cv ? pge * kBnC : 0.f;
+      colp[3][tid] = (cv && tid < a.h1) ? pg1 * kBnC : 0.f;
+      colp[4][tid] = (cv && tid < a.h1) ? pb1 : 0.f;
+    }
     const float pw = a.pos_weight;
     if (rv && !(kdbg(a.dbg) & 1)) {
       const __amdgpu_buffer_rsrc_t rsd = rows_rsrc(a.zb, (long long)a.R * L * 2);
-      gather_rows16<NQ>(a.colidx, a.rowptr[r], a.rowptr[r + 1], rsd, 2u * L, sub,
+      gather_rows16<NQ>(a.colidx, rp0, rp1, rsd, 2u * L, sub,
                         [&](int, const u32x4 (&v)[NQ], bool valid) {
         float zj[NQ][8], dot = 0.f;
 #pragma unroll
@@ -469,17 +513,27 @@ __global__ void __launch_bounds__(HR * 8) head_bwd_kernel(HeadBwdArgs a) {
       if (rv && qv[q]) {
         const float* msr = a.ms + (long long)r * L2;
         const long long ie = (long long)r * L + c0;
+        // the ten operand quads go out as one group (the split partials, when there are
+        // any, follow: their loop sat between the loads and cut them into three waits)
+        float4 muq[2], lsq[2], epq[2], djq[2], ddq[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          const float4 mu = *reinterpret_cast<const float4*>(msr + c0 + 4 * h);
-          const float4 ls = *reinterpret_cast<const float4*>(msr + L + c0 + 4 * h);
-          const float4 ep = *reinterpret_cast<const float4*>(a.eps + ie + 4 * h);
-          float4 dj = *reinterpret_cast<const float4*>(a.dJd + ie + 4 * h);
-          for (int sx = 0; sx < a.nextra; ++sx) {   // zzt_split_sum_kernel's order
+          muq[h] = *reinterpret_cast<const float4*>(msr + c0 + 4 * h);
+          lsq[h] = *reinterpret_cast<const float4*>(msr + L + c0 + 4 * h);
+          epq[h] = *reinterpret_cast<const float4*>(a.eps + ie + 4 * h);
+          djq[h] = *reinterpret_cast<const float4*>(a.dJd + ie + 4 * h);
+          ddq[h] = *reinterpret_cast<const float4*>(a.dz_dec + ie + 4 * h);
+        }
+        for (int sx = 0; sx < a.nextra; ++sx) {   // zzt_split_sum_kernel's order
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
             const float4 e = *reinterpret_cast<const float4*>(a.dJd_extra + (long long)sx * a.R * L + ie + 4 * h);
-            dj.x += e.x; dj.y += e.y; dj.z += e.z; dj.w += e.w;
+            djq[h].x += e.x; djq[h].y += e.y; djq[h].z += e.z; djq[h].w += e.w;
           }
-          const float4 dd = *reinterpret_cast<const float4*>(a.dz_dec + ie + 4 * h);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float4 mu = muq[h], ls = lsq[h], ep = epq[h], dj = djq[h], dd = ddq[h];
           const float m4[4] = {mu.x, mu.y, mu.z, mu.w}, l4[4] = {ls.x, ls.y, ls.z, ls.w};
           const float e4[4] = {ep.x, ep.y, ep.z, ep.w}, j4[4] = {dj.x, dj.y, dj.z, dj.w};
           const float d4[4] = {dd.x, dd.y, dd.z, dd.w};
@@ -555,19 +609,35 @@ __global__ void __launch_bounds__(HR * 8) head_bwd_kernel(HeadBwdArgs a) {
     }
   }
   // ENC1 epilogue operands: P1 for the B1 part, X for the feature part
+  // One unconditional group: a quad of columns lies wholly in the P1 part or wholly in the
+  // feature part (h1 % 4 == 0), so each takes one 16-byte P1 load and its feature loads,
+  // both with clamped indices, and the select follows.
   f32x4 ypf[NB2];
   unsigned cvm[NB2];
+  {
+    const long long rcl = min(r, a.R - 1);
+    const int fx = a.W - a.h1;   // feature columns
+    f32x4 pq[NB2];
+    float xq[NB2][4];
 #pragma unroll
-  for (int i = 0; i < NB2; ++i) {
-    ypf[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    cvm[i] = 0u;
-    const int nb = NB2 * half + i;
+    for (int i = 0; i < NB2; ++i) {
+      const int n0 = 16 * (NB2 * half + i) + 4 * lg;
+      pq[i] = *reinterpret_cast<const f32x4*>(a.p1 + rcl * a.h1 + min(n0, a.h1 - 4));
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = 16 * nb + 4 * lg + e;
-      if (nb < (a.np2 >> 4) && n < a.W) {
-        cvm[i] |= 1u << e;
-        if (vrow) ypf[i][e] = n < a.h1 ? a.p1[(long long)r * a.h1 + n] : a.x[(long long)r * a.ldx + (n - a.h1)];
+      for (int e = 0; e < 4; ++e) xq[i][e] = a.x[rcl * a.ldx + min(max(n0 + e - a.h1, 0), max(fx - 1, 0))];
+    }
+#pragma unroll
+    for (int i = 0; i < NB2; ++i) {
+      ypf[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      cvm[i] = 0u;
+      const int nb = NB2 * half + i;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int n = 16 * nb + 4 * lg + e;
+        if (nb < (a.np2 >> 4) && n < a.W) {
+          cvm[i] |= 1u << e;
+          if (vrow) ypf[i][e] = n < a.h1 ? pq[i][e] : xq[i][e];
+        }
       }
     }
   }
@@ -616,14 +686,11 @@ __global__ void __launch_bounds__(HR * 8) head_bwd_kernel(HeadBwdArgs a) {
       }
       if (!(kdbg(a.dbg) & 8)) {
         __bf16* op = a.dp1 + (long long)r * a.h1 + n0;
-        if (sm == 15u) {
+        if (sm == 15u) {   // h1 % 4 == 0: a quad is stored whole (P1 part) or not at all
           bf16x4 v4;
 #pragma unroll
           for (int e = 0; e < 4; ++e) v4[e] = (__bf16)o[e];
           *reinterpret_cast<bf16x4*>(op) = v4;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) if (sm >> e & 1u) op[e] = (__bf16)o[e];
         }
       }
 #pragma unroll
@@ -661,6 +728,59 @@ int head_bwd_launch(const HeadBwdArgs& a, hipStream_t s) {
   return 0;
 }
 
+// AX of the fused front for one CSR row [s, e), lane sub of its 8 (gcn0_kernel's sums: two
+// neighbours per lane and round, in its order), and the row's own features.  The ids of the
+// first 32 neighbours go out together, then all their features; every load is
+// unconditional (index clamped to the row's last entry, the select after the load).
+template <int F>
+__device__ __forceinline__ void front_ax(const float* x, int ldx, const int* colidx, int s, int e, int sub,
+                                         int rc, float (&ax)[4], float (&xown)[4]) {
+  feat_row<F, 4>(x, ldx, rc, xown);
+  if (s >= e) return;
+  const int last = e - 1;
+  int c[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) c[u] = colidx[min(s + sub + 8 * u, last)];
+  // (the empty asm statements keep the compiler from sinking a load into a branch on the
+  // select that consumes it, which is how the per-element waits came about)
+#pragma unroll
+  for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(c[u]));
+  float v[4][4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) feat_row<F, 4>(x, ldx, c[u], v[u]);
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int j = 0; j < F; ++j) asm volatile("" : "+v"(v[u][j]));
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int k = s + sub + 16 * t;
+    const bool p0 = k < e, p1 = k + 8 < e;
+    // a pair round adds v0 + v1, the tail round v0 alone; a round past the row end adds
+    // nothing (ax is never -0, so + (+0) leaves its bits)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float v0 = p0 ? v[2 * t][j] : 0.f, v1 = p1 ? v[2 * t + 1][j] : 0.f;
+      ax[j] += p1 ? v0 + v1 : v0;
+    }
+  }
+  int k = s + sub + 32;
+  for (; k + 8 < e; k += 16) {   // beyond 32 neighbours: the plain two-per-lane rounds
+    const int c0 = colidx[k], c1 = colidx[k + 8];
+    float v0[4], v1[4];
+    feat_row<F, 4>(x, ldx, c0, v0);
+    feat_row<F, 4>(x, ldx, c1, v1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ax[j] += v0[j] + v1[j];
+  }
+  if (k < e) {
+    float v0[4];
+    feat_row<F, 4>(x, ldx, colidx[k], v0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ax[j] += v0[j];
+  }
+}
+
 // ---------------------------------------------------------------- encoder front
 // One 128-row tile per workgroup: AX by the gcn0 gather (8 lanes per row, the fp32
 // features of the neighbours), H1 = [BN0(lrelu(AX W0)) | X] to HBM (the W1 weight
@@ -687,54 +807,64 @@ __global__ void __launch_bounds__(1024) enc_front_kernel(FrontArgs a) {
   __bf16* himg = reinterpret_cast<__bf16*>(smem + a.np1 * a.kp1 * 2);
   const int r0 = blockIdx.x * 128;
   const int K1 = a.h0 + a.f;
-  for (int i = tid; i < a.h0; i += 1024) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sp[q][i] = q < a.f ? a.w0[q * a.h0 + i] : 0.f;
-    sp[4][i] = a.g0[i] * kBnC;
-    sp[5][i] = a.b0[i];
-  }
-  __syncthreads();   // sp[] (read by the H1 math below)
-  // W1 image [np1][kp1]: element (n, k) = W1[k][n] (pack mode 0).  Its loads are issued
-  // before the A X gather and written to LDS after it, so their latency overlaps the
-  // gather's dependent rowptr -> colidx -> x chain instead of preceding it (np1 * kp1 / 8
-  // <= 1024 chunks: one per thread at the C2 widths, loops otherwise)
-  const int kc = a.kp1 >> 3;
-  const bool w1one = a.np1 * kc <= 1024;
-  float w1v[8];
-  if (w1one && tid < a.np1 * kc) {
-    const int c = tid % kc, n = tid / kc;
-    const int lc = c ^ img_swz(n, a.kp1);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = 8 * lc + j;
-      w1v[j] = (k < K1 && n < a.n1) ? a.w1[k * a.n1 + n] : 0.f;
-    }
-  }
-  // ---- AX for row rs (gcn0_kernel: two neighbours in flight per lane)
+  // Every global operand that does not depend on another load is requested here, in one
+  // group and unconditionally (index clamped into range, the select to zero after the
+  // load): parameters, the W1 chunk, the row's CSR bounds and its own features.  A load
+  // inside a per-element branch got a wait of its own in the compiled code, so these
+  // were ~25 dependent round trips; now the tile pays one for this group, one for the
+  // neighbour ids and one for the neighbour features.
   const int rs = tid >> 3, sub = tid & 7;
   const int r = r0 + rs;
   const bool rv = r < a.R;
-  float ax[4] = {0.f, 0.f, 0.f, 0.f};
-  if (rv) {
-    const int s = a.rowptr[r], e = a.rowptr[r + 1];
-    int k = s + sub;
-    for (; k + 8 < e; k += 16) {
-      const int c0 = a.colidx[k], c1 = a.colidx[k + 8];
-      float v0[4], v1[4];
+  const int fm = a.f - 1;
+  const int pi = min(tid, a.h0 - 1);
+  float spv[6];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v0[j] = j < a.f ? a.x[(long long)c0 * a.ldx + j] : 0.f;
-        v1[j] = j < a.f ? a.x[(long long)c1 * a.ldx + j] : 0.f;
-      }
+  for (int q = 0; q < 4; ++q) spv[q] = a.w0[min(q, fm) * a.h0 + pi];
+  spv[4] = a.g0[pi];
+  spv[5] = a.b0[pi];
+  // W1 image [np1][kp1]: element (n, k) = W1[k][n] (pack mode 0); np1 * kp1 / 8 <= 1024
+  // chunks: one per thread at the C2 widths (loaded here, converted and written to LDS
+  // after the gather), a loop otherwise
+  const int kc = a.kp1 >> 3;
+  const bool w1one = a.np1 * kc <= 1024;
+  const int wc = tid % kc, wn = tid / kc;
+  const int wlc = wc ^ img_swz(wn, a.kp1);
+  float w1v[8];
+  if (w1one) {
+    const int nn = min(wn, a.n1 - 1);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) ax[j] += v0[j] + v1[j];
-    }
-    if (k < e) {
-      const int c0 = a.colidx[k];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ax[j] += j < a.f ? a.x[(long long)c0 * a.ldx + j] : 0.f;
-    }
+    for (int j = 0; j < 8; ++j) w1v[j] = a.w1[min(8 * wlc + j, K1 - 1) * a.n1 + nn];
   }
+  const int rc = min(r, a.R - 1);
+  const int s = a.rowptr[rc], e1 = a.rowptr[rc + 1];
+  const int e = rv ? e1 : s;
+  // ---- own features and AX for row rs, one instantiation per feature count: a row's F
+  // features are one load
+  float ax[4] = {0.f, 0.f, 0.f, 0.f}, xown[4];
+  switch (a.f) {
+    case 1: front_ax<1>(a.x, a.ldx, a.colidx, s, e, sub, rc, ax, xown); break;
+    case 2: front_ax<2>(a.x, a.ldx, a.colidx, s, e, sub, rc, ax, xown); break;
+    case 3: front_ax<3>(a.x, a.ldx, a.colidx, s, e, sub, rc, ax, xown); break;
+    default: front_ax<4>(a.x, a.ldx, a.colidx, s, e, sub, rc, ax, xown); break;
+  }
+  // the sums leave the per-F code as plain runtime values: with ax[F..3] known to be zero
+  // the compiler contracted the H1 products below differently from gcn0_kernel's epilogue
+  // (one bf16 ulp on an element that cancels to ~1e-5), and H1 is held bitwise to it
+#pragma unroll
+  for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(ax[j]));
+  // the W1 values are consumed from here on: without this the compiler converts them
+  // right behind their loads, and that wait precedes the rowptr request
+  if (w1one)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(w1v[j]));
+  if (tid < a.h0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sp[q][tid] = q < a.f ? spv[q] : 0.f;
+    sp[4][tid] = spv[4] * kBnC;
+    sp[5][tid] = spv[5];
+  }
+  __syncthreads();   // sp[] (read by the H1 math below)
 #pragma unroll
   for (int j = 0; j < 4; ++j) ax[j] = row8_sum(ax[j]);
   // ---- H1 = [BN0(lrelu(AX W0)) | X]: lane sub owns chunk sub; the X chunk is chunk h0 / 8
@@ -756,7 +886,7 @@ __global__ void __launch_bounds__(1024) enc_front_kernel(FrontArgs a) {
   if (xo >= 0 && rv) {
     float xv[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) xv[j] = j < a.f ? a.x[(long long)r * a.ldx + j] : 0.f;
+    for (int j = 0; j < 8; ++j) xv[j] = (j < 4 && j < a.f) ? xown[j & 3] : 0.f;   // f <= 4 (front_supported)
     hx = to_bf16x8(xv);
   }
   {
@@ -769,22 +899,21 @@ __global__ void __launch_bounds__(1024) enc_front_kernel(FrontArgs a) {
   }
   if (w1one) {
     if (tid < a.np1 * kc) {
-      const int c = tid % kc, n = tid / kc;
       bf16x8 v;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (__bf16)w1v[j];
-      *reinterpret_cast<bf16x8*>(wimg + n * a.kp1 + 8 * c) = v;
+      for (int j = 0; j < 8; ++j) v[j] = (__bf16)((8 * wlc + j < K1 && wn < a.n1) ? w1v[j] : 0.f);
+      *reinterpret_cast<bf16x8*>(wimg + wn * a.kp1 + 8 * wc) = v;
     }
   } else {
     for (int i = tid; i < a.np1 * kc; i += 1024) {
       const int c = i % kc, n = i / kc;
       const int lc = c ^ img_swz(n, a.kp1);
+      float wv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) wv[j] = a.w1[min(8 * lc + j, K1 - 1) * a.n1 + min(n, a.n1 - 1)];
       bf16x8 v;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 8 * lc + j;
-        v[j] = (__bf16)((k < K1 && n < a.n1) ? a.w1[k * a.n1 + n] : 0.f);
-      }
+      for (int j = 0; j < 8; ++j) v[j] = (__bf16)((8 * lc + j < K1 && n < a.n1) ? wv[j] : 0.f);
       *reinterpret_cast<bf16x8*>(wimg + n * a.kp1 + 8 * c) = v;
     }
   }
@@ -866,7 +995,7 @@ int head_tiles(int R) { return cdiv(R, head_bwd_rows(R)); }
 bool head_bwd_supported(int L, int gh, int W, int h1, int kp1, int np1, int kp2, int np2) {
   if ((L != 16 && L != 32 && L != 64) || kp1 != 2 * L) return false;
   if (gh % 16 || gh < 16 || np1 != gh || np1 > 64 || gh > kp2 || (kp2 != 32 && kp2 != 64 && kp2 != 128)) return false;
-  if (W > 128 || np2 != (int)round_up(W, 16) || h1 % 4 || h1 > W) return false;
+  if (W > 128 || np2 != (int)round_up(W, 16) || h1 % 4 || h1 < 4 || h1 > W) return false;
   return BwdLay(kp1, np1, kp2, np2, L).total + kBwdStaticLds <= 160 * 1024;
 }
 
@@ -875,6 +1004,7 @@ int launch_head_bwd(const HeadBwdArgs& a, hipStream_t s) {
   SND_CHECK_ARG(head_bwd_supported(a.L, a.gh, a.W, a.h1, a.kp1, a.np1, a.kp2, a.np2),
                 "head_bwd: unsupported widths (L %d gh %d W %d h1 %d)", a.L, a.gh, a.W, a.h1);
   SND_CHECK_ARG((long long)a.R * a.L * 2 < (1ll << 31), "head_bwd: rows x L beyond the 2 GB buffer range");
+  SND_CHECK_ARG((reinterpret_cast<uintptr_t>(a.p1) & 15) == 0, "head_bwd: P1 must be 16-byte aligned");
   SND_CHECK_ARG(a.rowptr && (a.colidx || a.R == 0) && a.zb && a.edge_part && a.ms && a.eps && a.dz_dec &&
                     a.dJd && a.dms && a.bms_part && a.wmsb_img && a.dh && a.bh_part && a.whb_img && a.ge &&
                     a.g1 && a.b1 && a.p1 && a.x && a.dp1 && a.enc1_part,

@@ -19,22 +19,34 @@ __device__ __forceinline__ void pack_chunk_vals(const PackDesc& d, int i, float 
   const int n = tn % d.np, t = tn / d.np;
   const int lc = c ^ img_swz(n, d.kp);          // logical chunk stored at physical chunk c
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = 8 * lc + j;
-    float val = 0.f;
-    for (int si = 0; si < d.nsrc; ++si) {
-      const PackSrc& s = d.s[si];
-      if (s.mode == 2) {                  // identity over [a0, a1)
-        if (k == n && k >= s.a0 && k < s.a1) val = 1.f;
-        continue;
+  for (int j = 0; j < 8; ++j) vals[j] = 0.f;
+  // per source (uniform over the launch) the chunk's 8 loads go out together and
+  // unconditionally: an element outside the source's window reads element 0 and keeps
+  // its value (a load inside a per-element branch is waited for on its own)
+  for (int si = 0; si < d.nsrc; ++si) {
+    const PackSrc& s = d.s[si];
+    if (s.mode == 2) {                  // identity over [a0, a1)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = 8 * lc + j;
+        if (k == n && k >= s.a0 && k < s.a1) vals[j] = 1.f;
       }
+      continue;
+    }
+    if (s.A <= 0 || s.B <= 0) continue;   // an empty source has no element 0 to read
+    bool in[8];
+    float wv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = 8 * lc + j;
       int aa, bb, tt;
       if (s.mode == 0) { bb = n - s.n_off + s.b0; aa = k - s.k_off + s.a0; tt = t; }
       else { aa = n - s.n_off + s.a0; bb = k - s.k_off + s.b0; tt = d.T - 1 - t; }
-      if (aa >= s.a0 && aa < s.a1 && bb >= s.b0 && bb < s.b1)
-        val = s.w[((long long)tt * s.A + aa) * s.B + bb];
+      in[j] = aa >= s.a0 && aa < s.a1 && bb >= s.b0 && bb < s.b1;
+      wv[j] = s.w[in[j] ? ((long long)tt * s.A + aa) * s.B + bb : 0ll];
     }
-    vals[j] = val;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) vals[j] = in[j] ? wv[j] : vals[j];
   }
 }
 __device__ __forceinline__ void pack_chunk_store(const PackDesc& d, int i, const float (&vals)[8]) {

@@ -22,8 +22,10 @@ def load(d):
         by[did][r["Counter_Name"]] = by[did].get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
         names[did] = r["Kernel_Name"]
     ids = sorted(by)
-    # last step = dispatches after the second-to-last adam kernel
-    ad = [i for i in ids if "adam" in names[i]]
+    # last step = dispatches after the second-to-last adam kernel (the final reduction
+    # when Adam rides in it, as tools/step_timeline.py)
+    key = "adam" if any("adam" in n for n in names.values()) else "reduce_kernel"
+    ad = [i for i in ids if key in names[i]]
     lo = ad[-2] if len(ad) >= 2 else ids[0] - 1
     step = [i for i in ids if lo < i <= ad[-1]]
     return [(names[i], by[i]) for i in step]
