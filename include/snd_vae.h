@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 17
+#define SND_ABI_VERSION 18
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -231,6 +231,29 @@ int snd_zzt_ce_rows(const float* z, int n, int d, int row0, int row1,
                     const int* rowptr, const int* colidx, float pos_weight, float norm,
                     double* stats, float* dz, void* workspace, size_t workspace_bytes,
                     int dtype, snd_stream_t stream);
+
+/* ---- edge-score evaluation of the inner-product decoder (forward only) -------
+ * What the reference's post-training evaluation needs (main.py:13-14 roc_auc_score /
+ * average_precision_score, main.py:423,467) without the logits or a dense predicted
+ * adjacency in HBM.  z [B*N, d] fp32 with row stride ldz >= d, 1 <= d <= 128, any
+ * N >= 1; the block-diagonal CSR as snd_zzt_ce takes it (colidx in any order within
+ * a row).  L = z z^T per graph on the fp32 matrix cores, k ascending from zero: bit
+ * for bit the fp32 fmaf chain snd_generate's generated_adj thresholds.
+ * Per graph b over the N^2 - N ordered off-diagonal pairs:
+ *   hist[b][label][bin] += 1   (int64 [B, 2, 2048]); label = 1 for a CSR entry,
+ *     bin = clamp(floor(64 L) + 1024, 0, 2047): width 1/64 over [-16, 16), bins 0
+ *     and 2047 collect the under- and overflow;
+ *   counts[b] = {TP, FP, FN, TN} (int64 [B, 4]) at the rule L > 0 (model.py:208), the
+ *     N diagonal pairs counted as TN: (TP + TN) / N^2 is main.py:334's accuracy.
+ * accumulate = 0 clears hist and counts on the stream first, 1 adds to them.  Integer
+ * sums only: the result does not depend on scheduling and is additive over batches
+ * and ranks.  Non-finite z is unspecified.  workspace: snd_zzt_eval_workspace()
+ * bytes (0 today; NULL is accepted then). */
+size_t snd_zzt_eval_workspace(int n_graphs, int n, int d);
+int snd_zzt_eval(const float* z, int ldz, int n_graphs, int n, int d,
+                 const int* rowptr, const int* colidx, long long* hist,
+                 long long* counts, int accumulate, void* workspace,
+                 size_t workspace_bytes, snd_stream_t stream);
 
 /* ---- a11: sigmoid head + MSE ----------------------------------------------
  * Replaces tf.nn.sigmoid(linear(...)) (model_joint.py:121,144) and the

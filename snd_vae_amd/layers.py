@@ -209,6 +209,43 @@ def inner_product_ce_rows(z, row0, row1, rowptr, colidx, pos_weight=1.0, norm=1.
     return stats, dz
 
 
+def zzt_eval(z, rowptr, colidx, n_graphs, n, hist=None, counts=None, accumulate=False):
+    """Edge-score counters of the inner-product decoder (snd_zzt_eval): L = z z^T per graph
+    on the fp32 matrix cores, binned and classified on chip; no logits in HBM.
+
+    z: float32 device tensor [n_graphs * n, d] with unit column stride (its row stride is
+    passed as ldz), 1 <= d <= 128.  Returns (hist, counts): int64 [n_graphs, 2, 2048]
+    (label x logit bin of width 1/64 over [-16, 16)) and [n_graphs, 4] = {TP, FP, FN, TN}
+    at L > 0 (metrics.EdgeCounts turns them into accuracy / F1 / ROC-AUC / AP).  Given
+    ``hist`` / ``counts`` are cleared first, or added to with ``accumulate``.  No host
+    synchronisation."""
+    if not (z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and (z.shape[1] == 1 or z.stride(1) == 1)):
+        raise ValueError("zzt_eval z: expected a float32 device tensor [rows, d] with unit column stride")
+    rows, d = z.shape
+    if n_graphs < 1 or n < 1 or rows != n_graphs * n:
+        raise ValueError(f"zzt_eval: z has {rows} rows, expected n_graphs * n = {n_graphs} * {n}")
+    for t, name, numel in ((rowptr, "rowptr", rows + 1), (colidx, "colidx", 1)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() >= numel):
+            raise ValueError(f"zzt_eval {name}: expected a contiguous int32 device tensor of >= {numel} elements")
+    if (hist is None) != (counts is None):
+        raise ValueError("zzt_eval: pass both hist and counts or neither")
+    if hist is None:
+        if accumulate:
+            raise ValueError("zzt_eval: accumulate needs hist and counts")
+        hist = torch.empty(n_graphs, 2, 2048, dtype=torch.int64, device=z.device)
+        counts = torch.empty(n_graphs, 4, dtype=torch.int64, device=z.device)
+    for t, name, shape in ((hist, "hist", (n_graphs, 2, 2048)), (counts, "counts", (n_graphs, 4))):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int64 and tuple(t.shape) == shape):
+            raise ValueError(f"zzt_eval {name}: expected a contiguous int64 device tensor {list(shape)}")
+    L = _lib.lib()
+    ldz = z.stride(0) if rows > 1 else max(d, z.stride(0))
+    wsb = L.snd_zzt_eval_workspace(n_graphs, n, d)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=z.device) if wsb else None
+    _lib.check(L.snd_zzt_eval(_P(z), ldz, n_graphs, n, d, _P(rowptr), _P(colidx), _P(hist), _P(counts),
+                              int(bool(accumulate)), _P(ws), wsb, _lib.stream_ptr()), "snd_zzt_eval")
+    return hist, counts
+
+
 def dense_to_csr(adj):
     """Reference dense adj_truth [B,N,N] -> (rowptr, colidx) on the device."""
     b, n, _ = adj.shape

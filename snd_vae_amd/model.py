@@ -16,6 +16,7 @@ Attributes named as in the reference (read back after a step):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Optional
 
@@ -245,6 +246,21 @@ class SGCNModelVAE:
         generated_spatial [B*N, 2], generated_node_feat [B*N, F], z, and
         z_mean / z_std for the encoding modes (all fresh tensors).
         """
+        n = self.cfg.n_nodes
+        adj = (torch.empty(self.n_graphs, n, n, dtype=torch.uint8, device=self.device)
+               if want_adj else None)
+        self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
+        out = {"generated_adj": adj,
+               "generated_spatial": self.generated_spatial.clone(),
+               "generated_node_feat": self.generated_node_feat.clone(),
+               "z": self.z_sg.clone()}
+        if mode in ("mean", "sample"):
+            out["z_mean"] = self.z_mean_sg.clone()
+            out["z_std"] = self.z_std_sg.clone()
+        return out
+
+    def _generate_launch(self, batch, mode, z, eps, seed, step, adj, stream):
+        """snd_generate on the plan's workspace (argument checks of generate())."""
         L = _lib.lib()
         m = _lib.GEN_MODES[mode]
         if mode in ("mean", "sample") and batch is None:
@@ -257,23 +273,46 @@ class SGCNModelVAE:
             src = src.to(device=self.device, dtype=torch.float32).contiguous()
             if tuple(src.shape) != (rh, self.cfg.latent):
                 raise ValueError(f"z/eps must be [{rh}, {self.cfg.latent}], got {tuple(src.shape)}")
-        n = self.cfg.n_nodes
-        adj = (torch.empty(self.n_graphs, n, n, dtype=torch.uint8, device=self.device)
-               if want_adj else None)
         step_t = torch.full((1,), step, dtype=torch.int32, device=self.device)
         bc = batch.c_struct() if batch is not None else None
         _lib.check(L.snd_generate(self.plan, C.byref(bc) if bc is not None else None,
                                   _lib.ptr(self.params), _lib.ptr(self.workspace), m,
                                   _lib.ptr(src), seed, _lib.ptr(step_t), _lib.ptr(adj),
                                   _lib.stream_ptr(stream)), "snd_generate")
-        out = {"generated_adj": adj,
-               "generated_spatial": self.generated_spatial.clone(),
-               "generated_node_feat": self.generated_node_feat.clone(),
-               "z": self.z_sg.clone()}
-        if mode in ("mean", "sample"):
-            out["z_mean"] = self.z_mean_sg.clone()
-            out["z_std"] = self.z_std_sg.clone()
-        return out
+
+    def evaluate(self, batch: DeviceBatch, mode: str = "mean", z: Optional[torch.Tensor] = None,
+                 eps: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0,
+                 out=None, stream=None):
+        """Edge-score counters of the decoded batch against its adjacency
+        (metrics.EdgeCounts): generate(..., want_adj=False)'s forward pass, then
+        snd_zzt_eval on the decoder input J (``joint_h``) and the batch's CSR.  Neither
+        the logits nor a predicted adjacency reach HBM.
+
+        The logits are the fp32 fmaf chains generate()'s ``generated_adj`` thresholds, so
+        TP + FP is its number of ones and ``accuracy`` is ``adj_accuracy`` exactly.
+        ``out``: an EdgeCounts over device tensors (EdgeCounts.zeros(B, device)) to add
+        to and return -- no host synchronisation, the read-back happens when a metric is
+        first used; None returns fresh counters.  ``batch`` supplies the labels in every
+        mode ("prior" / "given" decode without encoding it).
+        """
+        from . import layers
+        from .metrics import EdgeCounts
+        if batch is None:
+            raise ValueError("evaluate needs the batch whose adjacency is the truth")
+        if batch.n_graphs != self.n_graphs or batch.n_nodes != self.cfg.n_nodes:
+            raise ValueError("evaluate: the batch does not match the plan's shape")
+        if out is not None and (not isinstance(out, EdgeCounts) or out.tensors is None):
+            raise ValueError("evaluate: out must be an EdgeCounts over device tensors")
+        enc = batch if mode in ("mean", "sample") else None
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            self._generate_launch(enc, mode, z, eps, seed, step, None, stream)
+            hist, counts = out.tensors if out is not None else (None, None)
+            hist, counts = layers.zzt_eval(self.joint_h, batch.rowptr, batch.colidx, self.n_graphs,
+                                           self.cfg.n_nodes, hist, counts, accumulate=out is not None)
+        if out is not None:
+            out.invalidate()
+            return out
+        return EdgeCounts(hist, counts)
 
 
 def adj_accuracy(gen_adj: torch.Tensor, batch: DeviceBatch) -> float:

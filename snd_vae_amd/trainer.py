@@ -149,6 +149,27 @@ class Trainer:
                     self.save(os.path.join(checkpoint_dir, f"model_dgt_global_{e}.safetensors"))
         return out
 
+    # -------------------------------------------------------------- evaluation
+    def evaluate(self, mode: str = "mean") -> dict:
+        """Link-prediction metrics of the current parameters over every batch (what the
+        reference's reconstruct_evaluation reports, `main.py:423`): accuracy, precision,
+        recall, F1, ROC-AUC, average precision and the best-F1 threshold
+        (metrics.EdgeCounts.summary), plus the summed counters under "edge_counts".
+
+        Forward passes only, outside the captured step graphs; all batches add into one
+        device buffer that is read back once, after the all-reduce when data parallel.
+        Parameters, Adam state and the step counter are not written."""
+        from .metrics import EdgeCounts
+        buf = EdgeCounts.zeros(self.model.n_graphs, device=self.model.params.device)
+        for b in self.batches:
+            self.model.evaluate(b, mode=mode, out=buf)
+        if self.opt.distributed:
+            buf = buf.all_reduce(self.opt.group)
+        tot = buf.total()
+        out = tot.summary()
+        out["edge_counts"] = tot
+        return out
+
     def save(self, path: str):
         ckpt.save(path, self.model, self.opt)
 
