@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 18
+#define SND_ABI_VERSION 19
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -254,6 +254,36 @@ int snd_zzt_eval(const float* z, int ldz, int n_graphs, int n, int d,
                  const int* rowptr, const int* colidx, long long* hist,
                  long long* counts, int accumulate, void* workspace,
                  size_t workspace_bytes, snd_stream_t stream);
+
+/* ---- edge extraction of the inner-product decoder (ABI 19; forward only) ------
+ * The predicted graph of the decoder at a caller-chosen logit threshold, written as the
+ * block-diagonal CSR of this header's preamble: what model.py:208's dense
+ * tf.cast(L > 0) is converted into before anything here can consume it.  z [B*N, d]
+ * fp32 with row stride ldz >= d, 1 <= d <= 128, any N >= 1 (the operand rules of
+ * snd_zzt_eval).  L = z z^T per graph is the logit snd_zzt_eval bins:
+ * v_mfma_f32_32x32x2_f32, k ascending from a zero accumulator, K zero-padded -- bit for
+ * bit the fp32 fmaf chain snd_generate's generated_adj thresholds.  So at threshold 0
+ * the CSR is np.nonzero(generated_adj) exactly, and at the threshold and rule that
+ * snd_zzt_eval's histogram selects it holds exactly the pairs that histogram counted.
+ *   (i, j) is an edge iff i != j and L_ij > threshold; L_ij >= threshold when
+ *   inclusive != 0.  -inf gives the complete graph, +inf the empty one; a NaN threshold
+ *   is SND_ERR_ARG before anything is launched.  Non-finite z is unspecified (no fault,
+ *   no write outside the outputs).
+ *   rowptr [B*N + 1] int32; colidx int32 global ids b*N + j, ascending within each row.
+ *   *nnz_out (device int64) always receives the exact number of edges; rowptr is
+ *   complete whenever that number is below 2^31.  colidx is written only when
+ *   colidx != NULL and the number is at most colidx_cap (and below 2^31); otherwise not
+ *   one element of it is touched and the call still returns 0 -- compare *nnz_out with
+ *   the capacity.  colidx = NULL (colidx_cap ignored) is the sizing call: count only.
+ * L is recomputed by the count and the fill pass; O(nnz) bytes reach HBM.  Integer
+ * results only: two runs on the same operands are bitwise equal.  workspace:
+ * snd_zzt_edges_workspace() bytes (0 for shapes the op rejects), 4-byte aligned. */
+size_t snd_zzt_edges_workspace(int n_graphs, int n, int d);
+int snd_zzt_edges(const float* z, int ldz, int n_graphs, int n, int d,
+                  float threshold, int inclusive,
+                  int* rowptr, int* colidx, long long colidx_cap,
+                  long long* nnz_out, void* workspace, size_t workspace_bytes,
+                  snd_stream_t stream);
 
 /* ---- a11: sigmoid head + MSE ----------------------------------------------
  * Replaces tf.nn.sigmoid(linear(...)) (model_joint.py:121,144) and the

@@ -9,50 +9,9 @@
 // into the workgroup's LDS histogram.  The flush adds the non-zero bins to the graph's
 // int64 histogram with 64-bit vector atomics.
 #include "snd_eval.hpp"
+#include "snd_zzt_tile.hpp"
 
 namespace snd {
-
-constexpr int kEvT = 128;    // tile rows and columns
-constexpr int kEvK = 32;     // k per staged chunk
-constexpr int kEvLd = 36;    // floats per staged row: 144-B rows put the 16 lanes of every
-                             // ds_read_b128 group on 16 distinct 16-B slots of the bank row
-
-// A staged row holds its 32 k permuted so that one 16-byte read gives a lane the operand
-// of four consecutive MFMAs: float 8q + 4h + s is k = 8q + 2s + h (h = lane >> 5 is the
-// instruction's k index, s the step), which keeps k ascending across the steps.
-// Staging is split into the global loads (into registers, issued one stage ahead so their
-// latency passes under the previous chunk's MFMAs) and the LDS stores.  Thread t holds k
-// 4j .. 4j + 3 (j = t & 7) of rows (t >> 3) + 32 i, i = 0 .. 3; rows past n and k past d are 0.
-__device__ __forceinline__ void eval_load(float4 (&v)[4], const float* Z, int ldz, int d, int n,
-                                          int rbase, int k0, bool vec, int tid) {
-  const int j = tid & 7, k = k0 + 4 * j;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = rbase + (tid >> 3) + 32 * i;
-    v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < n && k < d) {
-      const float* p = Z + (long long)row * ldz + k;
-      if (vec && k + 3 < d) {
-        v[i] = *reinterpret_cast<const float4*>(p);
-      } else {
-        v[i].x = p[0];
-        if (k + 1 < d) v[i].y = p[1];
-        if (k + 2 < d) v[i].z = p[2];
-        if (k + 3 < d) v[i].w = p[3];
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ void eval_store(float* s, const float4 (&v)[4], int tid) {
-  const int j = tid & 7;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float* dst = s + ((tid >> 3) + 32 * i) * kEvLd + (j >> 1) * 8 + (j & 1) * 2;
-    *reinterpret_cast<float2*>(dst) = make_float2(v[i].x, v[i].z);
-    *reinterpret_cast<float2*>(dst + 4) = make_float2(v[i].y, v[i].w);
-  }
-}
 
 // The cell of a logit: label * 2048 + clamp(floor(64 L) + 1024, 0, 2047).  The clamp is
 // done in float and once more on the integer, so no input (non-finite z is unspecified, but
@@ -236,6 +195,8 @@ __global__ void __launch_bounds__(256, 2) zzt_eval_kernel(ZztEvalArgs a) {
           }
         }
       }
+      // eval_mfma_chunk (snd_zzt_tile.hpp) spelled out: calling the helper here moves this
+      // kernel's register allocation (251 -> 256 VGPRs), so its loop stays in place
       const int rem = a.d - k0;
       const int nq = rem >= kEvK ? kEvK / 8 : (rem + 7) >> 3;
       for (int q = 0; q < nq; ++q) {

@@ -237,6 +237,39 @@ def batch_from_dense(cfg: SNDConfig, adj: np.ndarray, feature: np.ndarray,
                       np.ascontiguousarray(x), np.ascontiguousarray(s))
 
 
+def generated_batch(cfg: SNDConfig, rowptr, colidx, node_feat, spatial, n_graphs: int) -> GraphBatch:
+    """A host GraphBatch from a generated graph: the block-diagonal CSR of
+    ``generate(adj_format="csr")`` / ``layers.zzt_edges`` (host arrays: rowptr [B*N + 1],
+    colidx global ids ascending within each row) with the generated node features
+    [B*N, num_feature] and coordinates [B*N, spatial_dim].  The encoder input is composed
+    as ``synthetic_batch`` composes it ([x || S] when ``cfg.encoder_coords``), so the
+    result goes back through ``DeviceBatch``."""
+    n = cfg.n_nodes
+    rows = n_graphs * n
+    rp = np.asarray(rowptr).astype(np.int64).reshape(-1)
+    if n_graphs < 1 or rp.shape[0] != rows + 1 or rp[0] != 0 or (np.diff(rp) < 0).any():
+        raise ValueError(f"generated_batch: rowptr must be a non-decreasing [{rows + 1}] array starting at 0")
+    ci = np.asarray(colidx).astype(np.int64).reshape(-1)[:int(rp[-1])]
+    if ci.shape[0] != rp[-1]:
+        raise ValueError(f"generated_batch: colidx has {ci.shape[0]} entries, rowptr ends at {int(rp[-1])}")
+    owner = np.repeat(np.arange(rows, dtype=np.int64), np.diff(rp))
+    if ((ci // n != owner // n) | (ci == owner)).any():
+        raise ValueError("generated_batch: an entry leaves its graph's block or lies on the diagonal")
+    inner = np.ones(ci.shape[0], bool)
+    if rows:
+        inner[rp[:-1][np.diff(rp) > 0]] = False              # the first entry of every row
+    if (np.diff(ci)[inner[1:]] <= 0).any():
+        raise ValueError("generated_batch: column ids must ascend within each row")
+    x = np.asarray(node_feat, np.float32).reshape(rows, -1)
+    s = np.asarray(spatial, np.float32).reshape(rows, -1)
+    if x.shape[1] != cfg.num_feature or s.shape[1] != cfg.spatial_dim:
+        raise ValueError(f"generated_batch: node_feat / spatial must be [{rows}, {cfg.num_feature}] / "
+                         f"[{rows}, {cfg.spatial_dim}]")
+    f = np.concatenate([x, s], 1) if cfg.encoder_coords else x
+    return GraphBatch(n_graphs, n, rp.astype(np.int32), ci.astype(np.int32),
+                      np.ascontiguousarray(f, np.float32), np.ascontiguousarray(x), np.ascontiguousarray(s))
+
+
 def locality_order(batch: GraphBatch) -> np.ndarray:
     """Processing order of the rows for the gather kernels (int32 [B*N]).
 

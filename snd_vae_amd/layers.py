@@ -246,6 +246,57 @@ def zzt_eval(z, rowptr, colidx, n_graphs, n, hist=None, counts=None, accumulate=
     return hist, counts
 
 
+def zzt_edges(z, n_graphs, n, threshold=0.0, inclusive=False, capacity=None):
+    """The predicted graph of the inner-product decoder as a CSR (snd_zzt_edges): L = z z^T
+    per graph on the fp32 matrix cores, thresholded on chip; neither the logits nor a dense
+    adjacency reach HBM.
+
+    z as for ``zzt_eval``.  (i, j) is an edge iff i != j and L_ij > threshold (>= with
+    ``inclusive``, the rule ``EdgeCounts.best_f1`` reports); +-inf are legal, NaN is not.
+    Returns (rowptr, colidx, nnz): the block-diagonal CSR with ascending global column ids,
+    as ``DeviceBatch`` / ``zzt_eval`` / ``inner_product_ce`` take it.
+
+    capacity=None: a sizing call, one host read of the total, ``colidx`` allocated exactly
+    and the op run again; ``nnz`` is an int.  capacity=k: one call and no host
+    synchronisation; ``colidx`` has k elements, ``nnz`` is an int64 device tensor [1] with
+    the exact total, and ``colidx`` is left untouched when the total exceeds k."""
+    if not (z.dtype == torch.float32 and z.dim() == 2 and (z.shape[1] == 1 or z.stride(1) == 1)):
+        raise ValueError("zzt_edges z: expected a float32 device tensor [rows, d] with unit column stride")
+    rows, d = z.shape
+    if n_graphs < 1 or n < 1 or rows != n_graphs * n:
+        raise ValueError(f"zzt_edges: z has {rows} rows, expected n_graphs * n = {n_graphs} * {n}")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("zzt_edges: threshold is NaN")
+    if capacity is not None and (int(capacity) != capacity or capacity < 0):
+        raise ValueError(f"zzt_edges: capacity must be a non-negative integer or None, got {capacity!r}")
+    if not z.is_cuda:
+        raise ValueError("zzt_edges z: expected a device tensor (there is no CPU path)")
+    L = _lib.lib()
+    ldz = z.stride(0) if rows > 1 else max(d, z.stride(0))
+    wsb = L.snd_zzt_edges_workspace(n_graphs, n, d)
+    ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=z.device)
+    rowptr = torch.empty(rows + 1, dtype=torch.int32, device=z.device)
+    nnz = torch.empty(1, dtype=torch.int64, device=z.device)
+
+    def run(colidx, cap):
+        _lib.check(L.snd_zzt_edges(_P(z), ldz, n_graphs, n, d, threshold, int(bool(inclusive)), _P(rowptr),
+                                   _P(colidx), cap, _P(nnz), _P(ws), ws.numel(), _lib.stream_ptr()),
+                   "snd_zzt_edges")
+
+    if capacity is not None:
+        colidx = torch.empty(max(int(capacity), 1), dtype=torch.int32, device=z.device)[:int(capacity)]
+        run(colidx, int(capacity))
+        return rowptr, colidx, nnz
+    run(None, 0)
+    total = int(nnz.item())
+    if total >= 2 ** 31:
+        raise ValueError(f"zzt_edges: {total} edges exceed the int32 CSR range")
+    colidx = torch.empty(max(total, 1), dtype=torch.int32, device=z.device)
+    run(colidx, total)
+    return rowptr, colidx[:total], total
+
+
 def dense_to_csr(adj):
     """Reference dense adj_truth [B,N,N] -> (rowptr, colidx) on the device."""
     b, n, _ = adj.shape

@@ -236,7 +236,8 @@ class SGCNModelVAE:
     # ---- evaluation / sampling (snd_generate)
     def generate(self, batch: Optional[DeviceBatch] = None, mode: str = "mean",
                  z: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
-                 seed: int = 0, step: int = 0, want_adj: bool = True, stream=None) -> dict:
+                 seed: int = 0, step: int = 0, want_adj: bool = True, stream=None,
+                 adj_format: str = "dense", threshold: float = 0.0, inclusive: bool = False) -> dict:
         """Forward-only decode (`main.py:358-469`, `model.py:163-169`).
 
         mode: "mean" (z = z_mean, reconstruction), "sample" (z = mu + eps e^s as
@@ -245,15 +246,37 @@ class SGCNModelVAE:
         Philox at (seed, step).  Returns generated_adj (uint8 [B, N, N]),
         generated_spatial [B*N, 2], generated_node_feat [B*N, F], z, and
         z_mean / z_std for the encoding modes (all fresh tensors).
+
+        adj_format="csr": the generated graph as the block-diagonal CSR instead
+        (layers.zzt_edges on the decoder input, no dense adjacency anywhere):
+        generated_rowptr, generated_colidx and generated_nnz (an int; one host read
+        sizes colidx), generated_adj None.  An edge is L > ``threshold``, or L >=
+        ``threshold`` with ``inclusive`` (the rule of EdgeCounts.best_f1); at the defaults
+        the CSR is np.nonzero of the dense generated_adj exactly.  The dense format
+        decides at L > 0 only.
         """
+        if adj_format not in ("dense", "csr"):
+            raise ValueError(f"adj_format must be 'dense' or 'csr', got {adj_format!r}")
+        if adj_format == "dense" and (threshold != 0.0 or inclusive):
+            raise ValueError("the dense generated_adj decides at L > 0 only: a threshold or "
+                             "inclusive needs adj_format='csr'")
         n = self.cfg.n_nodes
+        csr = adj_format == "csr"
         adj = (torch.empty(self.n_graphs, n, n, dtype=torch.uint8, device=self.device)
-               if want_adj else None)
-        self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
+               if want_adj and not csr else None)
+        if csr:
+            from . import layers
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                self._generate_launch(batch, mode, z, eps, seed, step, None, stream)
+                rowptr, colidx, nnz = layers.zzt_edges(self.joint_h, self.n_graphs, n, threshold, inclusive)
+        else:
+            self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
         out = {"generated_adj": adj,
                "generated_spatial": self.generated_spatial.clone(),
                "generated_node_feat": self.generated_node_feat.clone(),
                "z": self.z_sg.clone()}
+        if csr:
+            out.update(generated_rowptr=rowptr, generated_colidx=colidx, generated_nnz=nnz)
         if mode in ("mean", "sample"):
             out["z_mean"] = self.z_mean_sg.clone()
             out["z_std"] = self.z_std_sg.clone()
@@ -269,7 +292,7 @@ class SGCNModelVAE:
         if mode == "given" and z is None:
             raise ValueError("mode 'given' needs z")
         if src is not None:
-            rh = self.n_graphs if self._graph_latent else self.n_graphs * self.cfg.n_nodes
+            rh = self.head_rows     # what snd_generate reads: B*S rows for the spatial-graph encoder
             src = src.to(device=self.device, dtype=torch.float32).contiguous()
             if tuple(src.shape) != (rh, self.cfg.latent):
                 raise ValueError(f"z/eps must be [{rh}, {self.cfg.latent}], got {tuple(src.shape)}")
