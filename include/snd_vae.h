@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 19
+#define SND_ABI_VERSION 20
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -284,6 +284,45 @@ int snd_zzt_edges(const float* z, int ldz, int n_graphs, int n, int d,
                   int* rowptr, int* colidx, long long colidx_cap,
                   long long* nnz_out, void* workspace, size_t workspace_bytes,
                   snd_stream_t stream);
+
+/* ---- graph statistics of a CSR and coordinates (ABI 20; forward only) ----------
+ * What the reference's reconstruct_evaluation / generation_evaluation (main.py:423,467;
+ * their utils/evaluation package is not shipped) are given: the graphs and the node
+ * coordinates.  Degree, triangle, local-clustering and edge-length statistics of B graphs
+ * x N nodes in one launch, from the block-diagonal CSR of this header's preamble (what
+ * snd_zzt_edges writes) without a host round trip.  1 <= N <= 32768.
+ *   N(i) = the SET of columns of row i inside i's graph block, i itself left out: entries
+ *   outside the block and self loops are ignored (as snd_zzt_eval ignores them), colidx in
+ *   any order within a row.  Duplicate entries give an unspecified count (no fault, no
+ *   store outside the outputs).
+ * Per row (R = B*N; deg and tri2 may each be NULL):
+ *   deg[i]  = |N(i)|
+ *   tri2[i] = sum_{j in N(i)} |N(i) & N(j)|   -- twice the triangles at i on a symmetric
+ *             CSR; the formula is the definition on an asymmetric one.
+ * Per graph b, hist [B, 3, 256] int64:
+ *   hist[b][0][min(deg, 255)] += 1                                    per node
+ *   hist[b][1][min(floor(256 tri2 / (deg (deg - 1))), 255)] += 1      per node, in 64-bit
+ *             integers; nodes with deg < 2 go to bin 0 (c = 0, networkx's convention)
+ *   hist[b][2][min(floor(len * len_scale), 255)] += 1   per entry with global column > row
+ *             inside the block, len = ||coords[i, :sd] - coords[j, :sd]||_2 in fp32
+ *             (coords [R, ldc] fp32, 1 <= sd <= 3, ldc >= sd, any alignment).  Left at
+ *             zero (unchanged under accumulate) when coords == NULL; sd, ldc and
+ *             len_scale are ignored then.  Non-finite coordinates: unspecified bin.
+ * totals [B, 4] int64 = {sum deg, sum tri2, sum deg (deg - 1), entries with column > row}:
+ *   density, mean degree, transitivity (sum tri2 / sum deg (deg - 1)) and the undirected
+ *   edge count follow.
+ * accumulate = 0 clears hist and totals on the stream first, != 0 adds to them.  Integer
+ * sums only: two runs are bitwise equal, and the result is additive over batches.
+ * SND_ERR_ARG before anything is launched: n_graphs < 1, n < 1, n > 32768; coords given
+ * with sd outside 1..3, ldc < sd or a NaN, negative or infinite len_scale; NULL rowptr,
+ * hist or totals; a workspace below snd_graph_stats_workspace() bytes (0 today; NULL is
+ * accepted then).  Work: sum_j deg(j)^2 column ids tested. */
+size_t snd_graph_stats_workspace(int n_graphs, int n);
+int snd_graph_stats(const int* rowptr, const int* colidx, int n_graphs, int n,
+                    const float* coords, int ldc, int sd, float len_scale,
+                    int* deg, int* tri2, long long* hist, long long* totals,
+                    int accumulate, void* workspace, size_t workspace_bytes,
+                    snd_stream_t stream);
 
 /* ---- a11: sigmoid head + MSE ----------------------------------------------
  * Replaces tf.nn.sigmoid(linear(...)) (model_joint.py:121,144) and the

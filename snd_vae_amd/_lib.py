@@ -17,7 +17,7 @@ c_int, c_ll, c_float, c_size, c_ull = C.c_int, C.c_longlong, C.c_float, C.c_size
 vp = C.c_void_p
 
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 GEN_MODES = {"sample": 0, "mean": 1, "prior": 2, "given": 3}
 TOPOLOGY = {"tscale": 0, "tref": 1, "sgjoint": 2}
 
@@ -103,6 +103,9 @@ _SIGS = {
     "snd_zzt_eval": (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, vp, vp, c_int, vp, c_size, vp]),
     "snd_zzt_edges_workspace": (c_size, [c_int, c_int, c_int]),
     "snd_zzt_edges": (c_int, [vp, c_int, c_int, c_int, c_int, c_float, c_int, vp, vp, c_ll, vp, vp, c_size, vp]),
+    "snd_graph_stats_workspace": (c_size, [c_int, c_int]),
+    "snd_graph_stats": (c_int, [vp, vp, c_int, c_int, vp, c_int, c_int, c_float, vp, vp, vp, vp, c_int, vp,
+                                c_size, vp]),
     "snd_sigmoid_mse_blocks": (c_int, [c_int]),
     "snd_sigmoid_mse": (c_int, [vp, c_int, c_int, c_int, vp, vp, c_int, vp, c_int, vp, vp,
                                 vp, c_int, vp, vp, vp, c_size, vp]),

@@ -297,6 +297,67 @@ def zzt_edges(z, n_graphs, n, threshold=0.0, inclusive=False, capacity=None):
     return rowptr, colidx[:total], total
 
 
+def graph_stats(rowptr, colidx, n_graphs, n, coords=None, max_len=None, hist=None, totals=None,
+                accumulate=False, per_node=False):
+    """Degree, triangle, local-clustering and edge-length statistics of a block-diagonal CSR
+    (snd_graph_stats), one launch, nothing read back.
+
+    rowptr / colidx: int32 device tensors as ``DeviceBatch`` holds and ``zzt_edges`` returns
+    them (entries outside a row's graph block and self loops are ignored).  coords: float32
+    device tensor [n_graphs * n, sd] with unit column stride, 1 <= sd <= 3, or None (no
+    edge-length histogram); ``max_len`` is the length the 256 bins span (bin width
+    max_len / 256, the last bin collects the overflow) and is required with coords.
+    Returns (hist, totals): int64 [n_graphs, 3, 256] (degree, clustering, edge length) and
+    [n_graphs, 4] = {sum deg, sum tri2, sum deg (deg - 1), entries with column > row}
+    (metrics.GraphStats turns them into density, transitivity, MMD ...); with ``per_node``
+    also (deg, tri2), int32 [n_graphs * n].  Given ``hist`` / ``totals`` are cleared first,
+    or added to with ``accumulate``.  No host synchronisation."""
+    if n_graphs < 1 or n < 1:
+        raise ValueError(f"graph_stats: expected n_graphs >= 1 and n >= 1, got {n_graphs} and {n}")
+    rows = n_graphs * n
+    # colidx may be empty (a generated graph without an edge): it is never read then
+    for t, name, numel in ((rowptr, "rowptr", rows + 1), (colidx, "colidx", 0)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() >= numel):
+            raise ValueError(f"graph_stats {name}: expected a contiguous int32 device tensor of >= {numel} elements")
+    ldc = sd = 0
+    len_scale = 0.0
+    if coords is not None:
+        if not (coords.is_cuda and coords.dtype == torch.float32 and coords.dim() == 2
+                and coords.shape[0] == rows and 1 <= coords.shape[1] <= 3
+                and (coords.shape[1] == 1 or coords.stride(1) == 1)):
+            raise ValueError(f"graph_stats coords: expected a float32 device tensor [{rows}, 1..3] with unit "
+                             "column stride")
+        if max_len is None or not (0.0 < float(max_len) < float("inf")):
+            raise ValueError(f"graph_stats: coords need a finite max_len > 0, got {max_len!r}")
+        sd = coords.shape[1]
+        ldc = coords.stride(0) if rows > 1 else max(sd, coords.stride(0))
+        len_scale = 256.0 / float(max_len)
+    elif max_len is not None:
+        raise ValueError("graph_stats: max_len without coords")
+    if (hist is None) != (totals is None):
+        raise ValueError("graph_stats: pass both hist and totals or neither")
+    dev = rowptr.device
+    if hist is None:
+        if accumulate:
+            raise ValueError("graph_stats: accumulate needs hist and totals")
+        hist = torch.empty(n_graphs, 3, 256, dtype=torch.int64, device=dev)
+        totals = torch.empty(n_graphs, 4, dtype=torch.int64, device=dev)
+    for t, name, shape in ((hist, "hist", (n_graphs, 3, 256)), (totals, "totals", (n_graphs, 4))):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int64 and tuple(t.shape) == shape):
+            raise ValueError(f"graph_stats {name}: expected a contiguous int64 device tensor {list(shape)}")
+    deg = tri2 = None
+    if per_node:
+        deg = torch.empty(rows, dtype=torch.int32, device=dev)
+        tri2 = torch.empty(rows, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    wsb = L.snd_graph_stats_workspace(n_graphs, n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+    _lib.check(L.snd_graph_stats(_P(rowptr), _P(colidx), n_graphs, n, _P(coords), ldc, sd, len_scale,
+                                 _P(deg), _P(tri2), _P(hist), _P(totals), int(bool(accumulate)), _P(ws), wsb,
+                                 _lib.stream_ptr()), "snd_graph_stats")
+    return (hist, totals, deg, tri2) if per_node else (hist, totals)
+
+
 def dense_to_csr(adj):
     """Reference dense adj_truth [B,N,N] -> (rowptr, colidx) on the device."""
     b, n, _ = adj.shape

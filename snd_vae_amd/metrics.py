@@ -11,6 +11,11 @@ diagonal counted as TN).  Everything here is a function of those integers, in
 float64; the counters are additive, so metrics of a dataset or of a
 data-parallel run are those of the summed counters, exactly.
 
+``GraphStats`` (below) is the generative side of the same evaluation: degree,
+clustering and edge-length histograms per graph from ``snd_graph_stats``, and the
+two-sample statistics (MMD with an EMD kernel, KL divergence) between a set of
+generated graphs and the data.
+
 Pure NumPy: imports without a GPU.  torch is imported only when a device tensor
 or a process group is handed in.
 """
@@ -236,3 +241,271 @@ class EdgeCounts:
 
     def __repr__(self) -> str:
         return f"EdgeCounts(n_graphs={self.n_graphs}, tp={self.tp}, fp={self.fp}, fn={self.fn}, tn={self.tn})"
+
+
+# ---------------------------------------------------------------------------
+# Graph statistics from the counters of ``snd_graph_stats``
+# ---------------------------------------------------------------------------
+GS_BINS = 256
+KINDS = ("degree", "clustering", "edge_length")
+
+
+def emd(p, q, width: float = 1.0) -> float:
+    """1-D earth mover's distance of two normalised histograms over the same bins of
+    width ``width``: sum |cdf_p - cdf_q| * width (the Wasserstein-1 distance of the two
+    distributions placed on the bin centres)."""
+    p = np.asarray(p, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64)
+    if p.shape != q.shape or p.ndim != 1:
+        raise ValueError("emd: expected two 1-D histograms over the same bins")
+    return float(np.sum(np.abs(np.cumsum(p) - np.cumsum(q))) * width)
+
+
+def _normalised(h: np.ndarray) -> np.ndarray:
+    """Rows of h scaled to sum 1; an empty row stays the zero histogram."""
+    h = h.astype(np.float64)
+    s = h.sum(axis=-1, keepdims=True)
+    return np.divide(h, s, out=np.zeros_like(h), where=s > 0)
+
+
+class GraphStats:
+    """hist [G, 3, 256] and totals [G, 4] of a set of G graphs of n nodes each
+    (``layers.graph_stats`` / ``snd_graph_stats``): per graph the histograms of the node
+    degree (bin = min(deg, 255)), of the local clustering coefficient (256 bins over
+    [0, 1], nodes of degree < 2 in bin 0) and of the edge length (256 bins of width
+    max_len / 256, the last one collecting longer edges), and totals = {sum deg,
+    sum tri2, sum deg (deg - 1), undirected edges}.
+
+    What the reference hands to ``reconstruct_evaluation`` / ``generation_evaluation``
+    (`main.py:423,467`) to answer: do generated graphs look like the data?  Built from
+    NumPy arrays or from two int64 torch tensors; device tensors are read back once, on
+    first use.  The histograms stay per graph, because the two-sample statistics (``mmd``)
+    are over *sets* of graphs; the scalar properties describe the set pooled, and
+    ``per_graph()`` gives them per graph.  ``max_len`` None: no edge lengths were binned.
+    """
+
+    def __init__(self, hist, totals, n: int, max_len=None):
+        self._dev = None
+        self._np = None
+        self.n = int(n)
+        self.max_len = None if max_len is None else float(max_len)
+        if self.n < 1:
+            raise ValueError("GraphStats: n must be >= 1")
+        if self.max_len is not None and not (0.0 < self.max_len < math.inf):
+            raise ValueError("GraphStats: max_len must be finite and > 0")
+        if _is_tensor(hist):
+            if (hist.dim() != 3 or tuple(hist.shape[1:]) != (3, GS_BINS)
+                    or tuple(totals.shape) != (hist.shape[0], 4)):
+                raise ValueError("GraphStats: expected hist [G, 3, 256] and totals [G, 4]")
+            self._dev = (hist, totals)
+        else:
+            h = np.asarray(hist, dtype=np.int64)
+            t = np.asarray(totals, dtype=np.int64)
+            if h.ndim == 2:
+                h, t = h[None], t.reshape(1, -1)
+            if h.ndim != 3 or h.shape[1:] != (3, GS_BINS) or t.shape != (h.shape[0], 4):
+                raise ValueError("GraphStats: expected hist [G, 3, 256] and totals [G, 4]")
+            self._np = (h, t)
+
+    # ---- storage
+    @property
+    def tensors(self):
+        """The (hist, totals) torch tensors this object was built on, or None."""
+        return self._dev
+
+    def invalidate(self) -> None:
+        """Forget the host copy: the device tensors were written since it was read."""
+        if self._dev is not None:
+            self._np = None
+
+    def _arrays(self) -> Tuple[np.ndarray, np.ndarray]:
+        if self._np is None:
+            import torch
+            h, t = self._dev
+            both = torch.cat([h.reshape(-1), t.reshape(-1)]).cpu().numpy()     # one read-back
+            k = h.numel()
+            self._np = (both[:k].reshape(tuple(h.shape)), both[k:].reshape(tuple(t.shape)))
+        return self._np
+
+    @property
+    def hist(self) -> np.ndarray:
+        return self._arrays()[0]
+
+    @property
+    def totals(self) -> np.ndarray:
+        return self._arrays()[1]
+
+    @property
+    def n_graphs(self) -> int:
+        return int((self._dev[0] if self._np is None else self._np[0]).shape[0])
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, GraphStats) and self.n == other.n and self.max_len == other.max_len
+                and np.array_equal(self.hist, other.hist) and np.array_equal(self.totals, other.totals))
+
+    __hash__ = None
+
+    @classmethod
+    def concat(cls, parts) -> "GraphStats":
+        """The graphs of several GraphStats (batches of one dataset) as one set, in order."""
+        parts = list(parts)
+        if not parts or not all(isinstance(p, GraphStats) for p in parts):
+            raise ValueError("GraphStats.concat: expected a non-empty list of GraphStats")
+        if any(p.n != parts[0].n or p.max_len != parts[0].max_len for p in parts):
+            raise ValueError("GraphStats.concat: the parts differ in n or max_len")
+        return cls(np.concatenate([p.hist for p in parts]), np.concatenate([p.totals for p in parts]),
+                   parts[0].n, parts[0].max_len)
+
+    def all_gather(self, process_group=None) -> "GraphStats":
+        """Every rank's graphs as one set, in rank order (data parallel; each rank holds the
+        same number of graphs), as a new GraphStats: the same on every rank."""
+        import torch
+        import torch.distributed as dist
+        dev = self._dev[0].device if self._dev is not None else torch.device("cpu")
+        if dev.type == "cpu" and dist.get_backend(process_group) == "nccl":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self._dev is not None and self._dev[0].device == dev:
+            h, t = self._dev
+        else:
+            h = torch.from_numpy(self.hist.copy()).to(dev)
+            t = torch.from_numpy(self.totals.copy()).to(dev)
+        flat = torch.cat([h.reshape(-1), t.reshape(-1)])
+        world = dist.get_world_size(process_group)
+        out = [torch.empty_like(flat) for _ in range(world)]
+        dist.all_gather(out, flat, group=process_group)
+        k = h.numel()
+        hs = torch.cat([o[:k].reshape(h.shape) for o in out])
+        ts = torch.cat([o[k:].reshape(t.shape) for o in out])
+        return GraphStats(hs, ts, self.n, self.max_len)
+
+    # ---- bins
+    def _kind(self, kind: str):
+        """(row of hist, bin width in the statistic's own units, default sigma)."""
+        if kind == "degree":
+            return 0, 1.0, 1.0
+        if kind == "clustering":
+            return 1, 1.0 / GS_BINS, 0.1
+        if kind == "edge_length":
+            if self.max_len is None:
+                raise ValueError("GraphStats: no edge lengths were binned (max_len is None)")
+            return 2, self.max_len / GS_BINS, 0.1 * self.max_len
+        raise ValueError(f"GraphStats: kind must be one of {KINDS}, got {kind!r}")
+
+    # ---- scalar properties
+    def _scalars(self, h: np.ndarray, t: np.ndarray, graphs) -> dict:
+        """Float64 properties of counters summed over their leading axis ``graphs``."""
+        n = self.n
+        t = t.astype(np.float64)
+        pairs = graphs * n * (n - 1.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = {"density": np.where(pairs > 0, t[..., 0] / np.where(pairs > 0, pairs, 1.0), NAN),
+                   "mean_degree": t[..., 0] / (graphs * float(n)),
+                   "transitivity": np.where(t[..., 2] > 0, t[..., 1] / np.where(t[..., 2] > 0, t[..., 2], 1.0), 0.0),
+                   "n_edges": t[..., 3]}
+            lower = np.arange(GS_BINS, dtype=np.float64) / GS_BINS
+            nodes = h[..., 1, :].sum(axis=-1).astype(np.float64)
+            out["mean_clustering"] = np.where(nodes > 0, (h[..., 1, :] * lower).sum(axis=-1)
+                                              / np.where(nodes > 0, nodes, 1.0), NAN)
+            if self.max_len is not None:
+                centres = (np.arange(GS_BINS, dtype=np.float64) + 0.5) * (self.max_len / GS_BINS)
+                e = h[..., 2, :].sum(axis=-1).astype(np.float64)
+                out["mean_edge_length"] = np.where(e > 0, (h[..., 2, :] * centres).sum(axis=-1)
+                                                   / np.where(e > 0, e, 1.0), NAN)
+        return out
+
+    def per_graph(self) -> dict:
+        """{property: float64 array [G]}: density = sum deg / (n (n - 1)), mean_degree,
+        transitivity = sum tri2 / sum deg (deg - 1) (0 without a wedge, as networkx),
+        n_edges (entries with column > row), mean_clustering from the bins' lower edges
+        (exact for c = 0; in all at most 1/256 below the exact mean) and, when lengths were
+        binned, mean_edge_length from the bin centres (nan for a graph without an edge)."""
+        return self._scalars(self.hist, self.totals, 1.0)
+
+    def summary(self) -> dict:
+        """The same properties of the set pooled, as floats (n_edges: the total)."""
+        s = self._scalars(self.hist.sum(axis=0), self.totals.sum(axis=0), float(self.n_graphs))
+        return {k: float(v) for k, v in s.items()}
+
+    density = property(lambda self: self.summary()["density"])
+    mean_degree = property(lambda self: self.summary()["mean_degree"])
+    transitivity = property(lambda self: self.summary()["transitivity"])
+    mean_clustering = property(lambda self: self.summary()["mean_clustering"])
+    n_edges = property(lambda self: int(self.totals[:, 3].sum()))
+
+    @property
+    def mean_edge_length(self) -> float:
+        return self.summary().get("mean_edge_length", NAN)
+
+    # ---- two-sample statistics
+    def _check_other(self, other, kind):
+        if not isinstance(other, GraphStats):
+            raise ValueError("GraphStats: expected another GraphStats")
+        row, width, sigma = self._kind(kind)
+        if kind == "edge_length" and other.max_len != self.max_len:
+            raise ValueError("GraphStats: the two sides binned edge lengths with different max_len")
+        return row, width, sigma
+
+    def mmd(self, other: "GraphStats", kind: str, sigma=None) -> float:
+        """Biased (V-statistic) MMD^2 between two sets of graphs over their per-graph
+        normalised histograms of ``kind``: mean k(a, a') + mean k(b, b') - 2 mean k(a, b),
+        k = exp(-EMD^2 / (2 sigma^2)), the EMD in the statistic's own units (degrees;
+        clustering in [0, 1] with bins of 1/256; length with bins of max_len / 256).
+        Default sigma: 1.0, 0.1 and 0.1 max_len.  A graph whose histogram is empty (no
+        edge, for "edge_length") enters as the zero histogram: its EMD to a graph with
+        edges is that graph's sum of cdf values, to another empty graph 0."""
+        row, width, s0 = self._check_other(other, kind)
+        sigma = s0 if sigma is None else float(sigma)
+        if not sigma > 0.0:
+            raise ValueError("GraphStats.mmd: sigma must be > 0")
+        ca = np.cumsum(_normalised(self.hist[:, row, :]), axis=1)
+        cb = np.cumsum(_normalised(other.hist[:, row, :]), axis=1)
+        if ca.shape[0] == 0 or cb.shape[0] == 0:
+            return NAN
+
+        def mean_k(x, y):
+            tot = 0.0
+            step = max(1, (1 << 22) // (y.shape[0] * GS_BINS))          # ~32 MB of float64 per block
+            for i in range(0, x.shape[0], step):
+                d = np.abs(x[i:i + step, None, :] - y[None, :, :]).sum(axis=2) * width
+                tot += float(np.exp(-(d * d) / (2.0 * sigma * sigma)).sum())
+            return tot / (x.shape[0] * y.shape[0])
+
+        return mean_k(ca, ca) + mean_k(cb, cb) - 2.0 * mean_k(ca, cb)
+
+    def pooled(self, kind: str) -> np.ndarray:
+        """The normalised histogram of ``kind`` over all graphs of the set."""
+        row, _, _ = self._kind(kind)
+        return _normalised(self.hist[:, row, :].sum(axis=0))
+
+    def kld(self, other: "GraphStats", kind: str, eps: float = 1e-12) -> float:
+        """KL(self || other) of the pooled normalised histograms, each smoothed by eps per
+        bin and renormalised (scipy.stats.entropy(p + eps, q + eps)).  nan when either side
+        has no count."""
+        self._check_other(other, kind)
+        p, q = self.pooled(kind), other.pooled(kind)
+        if p.sum() == 0 or q.sum() == 0:
+            return NAN
+        p = (p + eps) / (p + eps).sum()
+        q = (q + eps) / (q + eps).sum()
+        return float(np.sum(p * np.log(p / q)))
+
+    def compare(self, other: "GraphStats") -> dict:
+        """mmd_<kind>, kld_<kind> and emd_<kind> (the EMD of the pooled histograms) for the
+        three kinds (edge_length only when both sides binned lengths), plus both sides'
+        pooled scalars under "self" and "other"."""
+        if not isinstance(other, GraphStats):
+            raise ValueError("GraphStats.compare: expected another GraphStats")
+        out = {}
+        for kind in KINDS:
+            if kind == "edge_length" and (self.max_len is None or other.max_len is None):
+                continue
+            _, width, _ = self._check_other(other, kind)
+            out[f"mmd_{kind}"] = self.mmd(other, kind)
+            out[f"kld_{kind}"] = self.kld(other, kind)
+            out[f"emd_{kind}"] = emd(self.pooled(kind), other.pooled(kind), width)
+        out["self"] = self.summary()
+        out["other"] = other.summary()
+        return out
+
+    def __repr__(self) -> str:
+        return f"GraphStats(n_graphs={self.n_graphs}, n={self.n}, max_len={self.max_len})"

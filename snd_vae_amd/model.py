@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from typing import Dict, Optional
 
 import numpy as np
@@ -237,7 +238,8 @@ class SGCNModelVAE:
     def generate(self, batch: Optional[DeviceBatch] = None, mode: str = "mean",
                  z: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                  seed: int = 0, step: int = 0, want_adj: bool = True, stream=None,
-                 adj_format: str = "dense", threshold: float = 0.0, inclusive: bool = False) -> dict:
+                 adj_format: str = "dense", threshold: float = 0.0, inclusive: bool = False,
+                 stats: bool = False) -> dict:
         """Forward-only decode (`main.py:358-469`, `model.py:163-169`).
 
         mode: "mean" (z = z_mean, reconstruction), "sample" (z = mu + eps e^s as
@@ -254,9 +256,15 @@ class SGCNModelVAE:
         ``threshold`` with ``inclusive`` (the rule of EdgeCounts.best_f1); at the defaults
         the CSR is np.nonzero of the dense generated_adj exactly.  The dense format
         decides at L > 0 only.
+
+        stats=True (CSR format only): also "generated_stats", a metrics.GraphStats over
+        device tensors from the generated CSR and generated_spatial (layers.graph_stats on
+        the same stream; edge lengths over [0, sqrt(spatial_dim)], the unit box's diagonal).
         """
         if adj_format not in ("dense", "csr"):
             raise ValueError(f"adj_format must be 'dense' or 'csr', got {adj_format!r}")
+        if stats and adj_format != "csr":
+            raise ValueError("stats=True needs adj_format='csr': the statistics are taken from the CSR")
         if adj_format == "dense" and (threshold != 0.0 or inclusive):
             raise ValueError("the dense generated_adj decides at L > 0 only: a threshold or "
                              "inclusive needs adj_format='csr'")
@@ -269,6 +277,8 @@ class SGCNModelVAE:
             with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
                 self._generate_launch(batch, mode, z, eps, seed, step, None, stream)
                 rowptr, colidx, nnz = layers.zzt_edges(self.joint_h, self.n_graphs, n, threshold, inclusive)
+                if stats:
+                    gstats = self._graph_stats(rowptr, colidx, self.generated_spatial)
         else:
             self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
         out = {"generated_adj": adj,
@@ -277,10 +287,28 @@ class SGCNModelVAE:
                "z": self.z_sg.clone()}
         if csr:
             out.update(generated_rowptr=rowptr, generated_colidx=colidx, generated_nnz=nnz)
+            if stats:
+                out["generated_stats"] = gstats
         if mode in ("mean", "sample"):
             out["z_mean"] = self.z_mean_sg.clone()
             out["z_std"] = self.z_std_sg.clone()
         return out
+
+    def _graph_stats(self, rowptr, colidx, coords):
+        """metrics.GraphStats over fresh device counters (current stream, no read-back)."""
+        from . import layers
+        from .metrics import GraphStats
+        max_len = math.sqrt(self.cfg.spatial_dim)
+        hist, totals = layers.graph_stats(rowptr, colidx, self.n_graphs, self.cfg.n_nodes, coords, max_len)
+        return GraphStats(hist, totals, self.cfg.n_nodes, max_len)
+
+    def graph_stats(self, batch: DeviceBatch, stream=None):
+        """Graph statistics (metrics.GraphStats) of a batch's own adjacency and
+        ``spatial_truth``: the data side of generation_evaluation (`main.py:467`)."""
+        if batch.n_graphs != self.n_graphs or batch.n_nodes != self.cfg.n_nodes:
+            raise ValueError("graph_stats: the batch does not match the plan's shape")
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return self._graph_stats(batch.rowptr, batch.colidx, batch.spatial_truth)
 
     def _generate_launch(self, batch, mode, z, eps, seed, step, adj, stream):
         """snd_generate on the plan's workspace (argument checks of generate())."""

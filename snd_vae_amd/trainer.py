@@ -170,6 +170,40 @@ class Trainer:
         out["edge_counts"] = tot
         return out
 
+    def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
+                            inclusive: bool = True, seed: int = 0) -> dict:
+        """Do generated graphs look like the data?  For every batch the graph statistics
+        (metrics.GraphStats: degree, local clustering and edge length per graph) of the
+        batch itself and of a graph generated at its shape: mode "prior" decodes z ~ N(0, 1)
+        (the reference's test_generation, `main.py:467`), "mean" the batch's reconstruction
+        (test_reconstruct, `main.py:423`).  An edge is L >= ``threshold`` (L > without
+        ``inclusive``); None takes ``evaluate()["best_f1_threshold"]`` of the same mode.
+
+        Returns ``dataset.compare(generated)`` (MMD, KL divergence and EMD per statistic,
+        both sides' pooled scalars) plus the two GraphStats under "dataset" and "generated"
+        and the threshold used.  Forward passes only, outside the captured step graphs;
+        parameters, Adam state and the step counter are not written.  Data parallel: every
+        rank's graphs are gathered, so all ranks return the same numbers."""
+        from .metrics import GraphStats
+        if mode not in ("prior", "mean"):
+            raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
+        if threshold is None:
+            threshold = self.evaluate(mode)["best_f1_threshold"]
+            if threshold != threshold:                  # no positive anywhere: nothing to tune on
+                raise ValueError("evaluate_generation: the dataset has no edge to choose a threshold by")
+        data, gen = [], []
+        for i, b in enumerate(self.batches):
+            data.append(self.model.graph_stats(b))
+            out = self.model.generate(b if mode == "mean" else None, mode=mode, seed=seed, step=i,
+                                      adj_format="csr", threshold=threshold, inclusive=inclusive, stats=True)
+            gen.append(out["generated_stats"])
+        data, gen = GraphStats.concat(data), GraphStats.concat(gen)
+        if self.opt.distributed:
+            data, gen = data.all_gather(self.opt.group), gen.all_gather(self.opt.group)
+        out = data.compare(gen)
+        out.update(dataset=data, generated=gen, threshold=threshold)
+        return out
+
     def save(self, path: str):
         ckpt.save(path, self.model, self.opt)
 
