@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 20
+#define SND_ABI_VERSION 21
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -397,6 +397,54 @@ int snd_sg_layer_bwd(const snd_sg_graph_t* g, const float* x, int ldx, int f, in
                      int h2, const float* params, int bn_act, const float* y,
                      const float* dout, float* dx, int lddx, float* grads, void* workspace,
                      snd_stream_t stream);
+
+/* ---- SpatialGraphConvolution_3D (ABI 21; layers.py:200-277), the three-hop layer
+ * the reference selects for its 3-D datasets (model.py:139-140; four widths per
+ * layer, main.py:223,241; spatial_dim 3), and the encoder layer
+ * s' = lrelu(BN(SGConv3D(adj, s, rel))).  The reference materialises
+ * B x N x N x N x N x (4F+5) messages; here the layer is factorised to O(P2 h0)
+ * vector work over the P2 = sum_j d_j^2 directed 2-paths, the two-hop layer's edge
+ * and node work and row / edge GEMMs (see snd_sg3.hip).  fp32 forward and backward,
+ * no floating-point atomics: two runs on the same operands are bitwise equal.
+ * Path indices need not be distinct (k may equal i, p may equal i or j), as in the
+ * reference.  adj must be symmetric with rel_dim 1; g is a prepared snd_sg_graph_t
+ * (snd_sg_prep) and rel the same dense [B, N, N] array snd_sg_prep read.
+ * Per-layer parameter buffer (fp32, snd_sg3_param_count floats), row-major:
+ *   Matrix0 [4F+5][h0] (rows: x_i | x_j | x_k | x_p | rel_ij | rel_jk | rel_kp |
+ *                       dis_ik | dis_ip), bias0 [h0],
+ *   Matrix1 [3F+3+h0][h1] (x_i | x_j | x_k | rel_ij | rel_jk | dis_ik | m4_sum), bias1 [h1],
+ *   Matrix2 [2F+1+h1][h2] (x_i | x_j | rel_ij | m3_sum), bias2 [h2],
+ *   Matrix3 [F+h2][h3] (x | m2_sum), bias3 [h3], BN gamma [h3], BN beta [h3].
+ * Gradients use the same layout (written, not accumulated).
+ * nnz = rowptr[R]; n_paths = sum over directed edges (i, j) of d_j, computed by the
+ * caller on the host (the kernels walk the paths from the CSR and recompute the
+ * per-path scalars, so n_paths is validated and reserved: the workspace of this
+ * version does not grow with it).  Every buffer is caller-owned; the entry points
+ * neither allocate nor synchronise.
+ * SND_ERR_ARG is returned before anything is launched, with a message naming the
+ * entry point and no buffer touched, for: ldx < f or lddx < f, a width below 1,
+ * bn_act without out, n_rows not a multiple of n_per_graph, nnz or n_paths below 0,
+ * a NULL required pointer (dx alone may be NULL), or workspace_bytes below
+ * snd_sg3_workspace().
+ * The fused SND_SGJOINT plan stays two-hop (snd_config_t.sg_h holds three widths per
+ * layer): a four-width configuration is SND_ERR_UNSUPPORTED there (a ValueError from
+ * the Python plan builder); compose this layer per call instead. */
+long long snd_sg3_param_count(int f, int h0, int h1, int h2, int h3);   /* -1: bad width */
+size_t snd_sg3_workspace(int n_rows, long long nnz, long long n_paths, int f, int h0, int h1,
+                         int h2, int h3);                               /* 0: bad argument */
+/* y [R, h3] = SGConv3D(adj, x, rel); bn_act: out = lrelu(BN(y)) (frozen Keras BN).
+ * The workspace keeps what snd_sg3_layer_bwd needs: pass the same one. */
+int snd_sg3_layer_fwd(const snd_sg_graph_t* g, const float* rel, long long nnz, long long n_paths,
+                      const float* x, int ldx, int f, int h0, int h1, int h2, int h3,
+                      const float* params, int bn_act, float* y, float* out, void* workspace,
+                      size_t workspace_bytes, snd_stream_t stream);
+/* dout = dL/d(out) (bn_act) or dL/dy; writes grads (param layout) and, if dx is
+ * not NULL, dL/dx [R, f] (row stride lddx). */
+int snd_sg3_layer_bwd(const snd_sg_graph_t* g, const float* rel, long long nnz, long long n_paths,
+                      const float* x, int ldx, int f, int h0, int h1, int h2, int h3,
+                      const float* params, int bn_act, const float* y, const float* dout,
+                      float* dx, int lddx, float* grads, void* workspace,
+                      size_t workspace_bytes, snd_stream_t stream);
 
 /* ---- §8f rank 4: disentangled-model pieces (ABI 8; not on the benchmarked path) -
  * e2e edge-to-edge filter of the structure decoder (layers.py:431-450), fp32:

@@ -17,7 +17,7 @@ c_int, c_ll, c_float, c_size, c_ull = C.c_int, C.c_longlong, C.c_float, C.c_size
 vp = C.c_void_p
 
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 GEN_MODES = {"sample": 0, "mean": 1, "prior": 2, "given": 3}
 TOPOLOGY = {"tscale": 0, "tref": 1, "sgjoint": 2}
 
@@ -120,6 +120,12 @@ _SIGS = {
                                  c_int, vp, vp, vp, vp]),
     "snd_sg_layer_bwd": (c_int, [C.POINTER(SGGraph), vp, c_int, c_int, c_int, c_int, c_int, vp,
                                  c_int, vp, vp, vp, c_int, vp, vp, vp]),
+    "snd_sg3_param_count": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
+    "snd_sg3_workspace": (c_size, [c_int, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int]),
+    "snd_sg3_layer_fwd": (c_int, [C.POINTER(SGGraph), vp, c_ll, c_ll, vp, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, vp, c_int, vp, vp, vp, c_size, vp]),
+    "snd_sg3_layer_bwd": (c_int, [C.POINTER(SGGraph), vp, c_ll, c_ll, vp, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, vp, c_int, vp, vp, vp, c_int, vp, vp, c_size, vp]),
     "snd_e2e_fwd": (c_int, [vp, c_int, c_int, c_int, vp, vp, c_int, c_int, vp, vp]),
     "snd_e2e_bwd": (c_int, [vp, c_int, c_int, c_int, vp, c_int, c_int, vp, vp, vp, vp, vp]),
     "snd_e2e_pair_fwd": (c_int, [vp, c_int, c_int, c_int, vp, vp, vp, vp]),

@@ -19,6 +19,7 @@ r = sqrt(kbar / (pi N)), edges from ``cKDTree.query_pairs``.
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -118,14 +119,24 @@ def make_sg_batch(base: GraphBatch, trees: Sequence[Sequence[np.ndarray]], rel: 
                    base.feature_truth, base.spatial_truth, S, trp, tci, np.ascontiguousarray(relc))
 
 
-def sgjoint_batch(cfg: SNDConfig, n_graphs: int, seed: Optional[int] = None) -> SGBatch:
+def sgjoint_batch(cfg: SNDConfig, n_graphs: int, seed: Optional[int] = None,
+                  spatial_dim: Optional[int] = None) -> SGBatch:
     """B seeded RGG graphs with cfg.sampling_num scipy-MST spanning trees each under
     U[1,2) edge weights (input_data.py:18-38, np.random.RandomState(seed)) and rel
-    from the node positions."""
+    from the node positions.  spatial_dim = 3 (the reference's 3-D datasets,
+    main.py:221,239): the planar positions get a third coordinate, so the points lie in
+    the unit cube, spatial_truth is [B*N, 3] and rel the 3-D Euclidean distance; graphs
+    and trees are the ones of the default (None: cfg.spatial_dim of the planar points)."""
     from .input_data import spanning_tree_edges
     seed = cfg.seed if seed is None else seed
     base = synthetic_batch(cfg, n_graphs, seed=seed)
     n = cfg.n_nodes
+    if spatial_dim is not None and spatial_dim != base.spatial_truth.shape[1]:
+        if spatial_dim != 3 or base.spatial_truth.shape[1] != 2:
+            raise ValueError("sgjoint_batch: spatial_dim is None (the config's) or 3 over planar points")
+        z = np.concatenate([np.random.default_rng([seed + b, 3]).random((n, 1)) for b in range(n_graphs)])
+        base = dataclasses.replace(base, spatial_truth=np.ascontiguousarray(
+            np.concatenate([base.spatial_truth, z.astype(np.float32)], 1)))
     rs = np.random.RandomState(seed)
     trees, rel = [], []
     for b in range(n_graphs):

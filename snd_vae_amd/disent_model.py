@@ -10,7 +10,8 @@ encoders, three latents, three decoders --
   coordinates, BN encoder_s, flat heads g_s1..3_lin;
 * spatial-graph encoder (`model.py:134-151`): two SpatialGraphConvolution layers over
   the B * sampling_num spanning-tree copies (lrelu after BN), BN encoder_sg, flat heads
-  per copy g_sg1..3_lin;
+  per copy g_sg1..3_lin; sg_conv_hidden entries of four widths select the three-hop
+  SpatialGraphConvolution_3D of the 3-D datasets (`model.py:139-140`, spatial_dim 3);
 * decoder (`model.py:172-222`): J_sg = mean over the copies of d_sg_lin1(z_sg)
   (`model.py:177,180`), J_s = d_s_lin1(z_s), J_g = d_g_lin1(z_g); node features from
   [J_sg | J_g] (conv1d + BN, no activation, x2; BN decoder_node; sigmoid(d_n_lin2)),
@@ -41,8 +42,8 @@ from .config import CONV_K
 from .data import SGBatch
 from .disent import disentangled_cost, structure_decoder
 from .layers import conv1d_same_bwd, graph_convolution, spmm
-from .params import _glorot_uniform, _truncated_normal, sg_layer_shapes
-from .sg import SGGraph, SpatialGraphConvolution
+from .params import _glorot_uniform, _truncated_normal
+from .sg import SGGraph, layer_param_shapes, make_layer
 
 _P = _lib.ptr
 
@@ -59,7 +60,9 @@ class DisentangledConfig:
     s_channel: Tuple[int, ...] = (10, 10, 20)                    # main.py:181
     s_hidden: int = 100
     s_latent: int = 100
-    sg_conv_hidden: Tuple[Tuple[int, int, int], ...] = ((20, 20, 20), (50, 50, 50))
+    # three widths per layer: SpatialGraphConvolution; four: SpatialGraphConvolution_3D, the
+    # reference's 3-D datasets ([[10]*4, [20]*4] / [[20]*4, [50]*4], main.py:223,241)
+    sg_conv_hidden: Tuple[Tuple[int, ...], ...] = ((20, 20, 20), (50, 50, 50))
     sg_hidden: int = 100
     sg_latent: int = 100
     sampling_num: int = 10                                       # main.py:100
@@ -108,9 +111,9 @@ def block_shapes(cfg: DisentangledConfig) -> "OrderedDict[str, Tuple[int, ...]]"
     s["g_s1_lin/Matrix"], s["g_s1_lin/bias"] = (N * c, cfg.s_hidden), (cfg.s_hidden,)
     s["g_s23_lin/Matrix"], s["g_s23_lin/bias"] = (cfg.s_hidden, 2 * cfg.s_latent), (2 * cfg.s_latent,)
     f = F
-    for i, hid in enumerate(cfg.sg_conv_hidden):                 # SG layer + its BN (snd_sg layout)
-        s[f"g_sg{i}_conv"] = (sum(int(np.prod(sh)) for _, sh in sg_layer_shapes(f, hid)),)
-        f = hid[2]
+    for i, hid in enumerate(cfg.sg_conv_hidden):                 # SG layer + its BN (snd_sg / snd_sg3 layout)
+        s[f"g_sg{i}_conv"] = (sum(int(np.prod(sh)) for _, sh in layer_param_shapes(f, hid)),)
+        f = hid[-1]
     _bn(s, "encoder_sg", f)
     s["g_sg1_lin/Matrix"], s["g_sg1_lin/bias"] = (N * f, cfg.sg_hidden), (cfg.sg_hidden,)
     s["g_sg23_lin/Matrix"], s["g_sg23_lin/bias"] = (cfg.sg_hidden, 2 * cfg.sg_latent), (2 * cfg.sg_latent,)
@@ -142,20 +145,20 @@ def block_shapes(cfg: DisentangledConfig) -> "OrderedDict[str, Tuple[int, ...]]"
 def init_blocks(cfg: DisentangledConfig, seed: int = 0) -> Dict[str, np.ndarray]:
     """The reference initialisers: GraphConvolution w and e2e w1 truncated-normal(0.02)
     (layers.py:119,435), linear Matrix N(0, 0.02) (layers.py:570), SG matrices
-    N(0, 0.02) (layers.py:158-169), conv1d glorot-uniform, biases 0, BN gamma 1 beta 0."""
+    N(0, 0.02) (layers.py:158-169,210-225), conv1d glorot-uniform, biases 0, BN gamma 1 beta 0."""
     rng = np.random.default_rng(seed)
     out = {}
     f = cfg.num_feature
     sg_in = {}
     for i, hid in enumerate(cfg.sg_conv_hidden):
         sg_in[f"g_sg{i}_conv"] = (f, hid)
-        f = hid[2]
+        f = hid[-1]
     for k, shp in block_shapes(cfg).items():
         if k in sg_in:
             fi, hid = sg_in[k]
             parts = [rng.normal(0.0, 0.02, sh).reshape(-1) if n.startswith("Matrix")
                      else (np.ones(sh) if n == "gamma" else np.zeros(sh)).reshape(-1)
-                     for n, sh in sg_layer_shapes(fi, hid)]
+                     for n, sh in layer_param_shapes(fi, hid)]
             v = np.concatenate(parts)
         elif k.endswith("_conv/w") or k.endswith("/w1"):
             v = _truncated_normal(rng, shp, 0.02)
@@ -235,8 +238,8 @@ class DisentangledSGCNModelVAE:
         f = cfg.num_feature
         self.sg_layers = []
         for i, hid in enumerate(cfg.sg_conv_hidden):
-            self.sg_layers.append(SpatialGraphConvolution(f, hid, self.w(f"g_sg{i}_conv")))
-            f = hid[2]
+            self.sg_layers.append(make_layer(f, hid, self.w(f"g_sg{i}_conv")))
+            f = hid[-1]
 
     # ---- parameters
     def w(self, k):
@@ -319,7 +322,7 @@ class DisentangledSGCNModelVAE:
         sg_in = batch.x_sg
         for layer in self.sg_layers:
             sg_in, _ = layer.forward(batch.sg_graph, sg_in)
-        Wsg = cfg.sg_conv_hidden[-1][2]
+        Wsg = cfg.sg_conv_hidden[-1][-1]
         sg_out = sg_in
         Vsg = T(RS, Wsg)
         _bn_act(sg_out, Wsg, RS, Wsg, self.w("encoder_sg/gamma"), self.w("encoder_sg/beta"), IDENT, False, Vsg, Wsg)

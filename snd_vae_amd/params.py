@@ -64,6 +64,9 @@ def block_shapes(cfg: SNDConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     if sg:
         if len(cfg.sg_conv_hidden) != 2:
             raise ValueError("sgjoint: two spatial-graph layers (the plan's encoder)")
+        if any(len(h) != 3 for h in cfg.sg_conv_hidden):
+            raise ValueError("sgjoint: the fused plan is two-hop (three widths per layer); the "
+                             "three-hop layer runs in sg.SGEncoder and DisentangledSGCNModelVAE")
         for i, (fi, hid) in enumerate(zip(sg_layer_inputs(cfg), cfg.sg_conv_hidden)):
             shapes[f"enc.sg{i}"] = (sum(int(np.prod(sh)) for _, sh in sg_layer_shapes(fi, hid)),)
     else:
