@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 21
+#define SND_ABI_VERSION 22
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -520,6 +520,49 @@ size_t snd_latent_reg_workspace(int batch, int latent);
 int snd_latent_reg(const float* mu, const float* logstd, const float* z, int batch, int latent,
                    const snd_latent_reg_t* w, float* dmu, float* dlogstd, double* out,
                    void* workspace, snd_stream_t stream);
+
+/* ---- forward-only e2e structure decoder (ABI 22) ------------------------------
+ * The generated adjacency of model.py:193-208 from z [n_graphs, n, d] (row stride ldz),
+ * without the CE and the gradients of snd_e2e_head_ce: reconstruction, sampling and
+ * latent traversal (model.py:163-169,227-358).
+ *   x0 = relu(BN0([z_i | z_j]));  per layer y = e2e(x) with K = n, TF SAME padding
+ *   (n-1)/2 before;  the next x = relu(BN(y));  logits = relu(BN_adj(y_last)) W + b,
+ *   the diagonal forced to (1, 0);  margin = l1 - l0 (-1 on the diagonal);  adj = 1 iff
+ *   l1 > l0 (a tie is 0, as tf.argmax; so the diagonal is 0).
+ * layers[l]: gamma / beta of the frozen Keras BN over the layer's INPUT channels (2 d for
+ * layer 0, cout of layer l-1 after it), w [n, cin, cout] (model.py:202), b [cout].
+ * head_gamma / head_beta [c_last] (decoder_adj), head_w [c_last][2], head_b [2] (d_e_lin2).
+ * adj [n_graphs, n, n] bytes; margin [n_graphs, n, n] floats or NULL.
+ * Layer 0 is factorised over the pair structure of its input (2 d multiply-adds per
+ * output, the pair tensor is never formed); later layers add the row and the column
+ * input before the shared taps.  BN + relu are applied as operands are loaded, the head
+ * and the argmax in the last layer's epilogue: no pair tensor, no stand-alone BN pass
+ * and no logits in device memory.  fp32 FMA, fixed summation order, no atomics (two runs
+ * are bitwise equal); no host synchronisation and no allocation (capturable in a graph).
+ * workspace >= snd_e2e_decode_workspace bytes (0 for a bad shape): at most two
+ * activations [n_graphs, n, n, max cout] (one with two layers, none with one), the
+ * per-node terms of layer 0 (2 n_graphs n cout_0 floats, sharing the second activation)
+ * and one [n, 2 d, cout_0] weight image.
+ * SND_ERR_ARG before anything touches the device: a null operand, n_layers < 1 (or > 16),
+ * a width < 1, n or a cout > 512, ldz < d, c_last > 32 (as snd_e2e_head_ce), a short
+ * workspace, n_graphs > 262140 (decode in chunks). */
+typedef struct {
+  const float *gamma, *beta;   /* frozen BN over the layer's input channels */
+  const float *w, *b;          /* w [n, cin, cout], b [cout] */
+  int cout;
+} snd_e2e_layer_t;
+size_t snd_e2e_decode_workspace(int n_graphs, int n, int d, const int* couts, int n_layers);
+int snd_e2e_decode(const float* z, int ldz, int n_graphs, int n, int d,
+                   const snd_e2e_layer_t* layers, int n_layers,
+                   const float* head_gamma, const float* head_beta,
+                   const float* head_w, const float* head_b,
+                   unsigned char* adj, float* margin,
+                   void* workspace, size_t workspace_bytes, snd_stream_t stream);
+/* yhat = sigmoid(u w + b): the forward half of snd_sigmoid_mse for the decoders'
+ * sigmoid heads at inference (no target).  u [rows, cin] (stride ldu), w [cin, cout],
+ * yhat [rows, cout] (stride ldy). */
+int snd_sigmoid_linear_fwd(const float* u, int ldu, long long rows, int cin, const float* w,
+                           const float* b, int cout, float* yhat, int ldy, snd_stream_t stream);
 
 /* ---- a14: the whole train step (main.py:315-334) ---------------------------
  * A plan fixes shapes; the step runs forward + backward of the SND-VAE

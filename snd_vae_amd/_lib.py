@@ -17,7 +17,7 @@ c_int, c_ll, c_float, c_size, c_ull = C.c_int, C.c_longlong, C.c_float, C.c_size
 vp = C.c_void_p
 
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 GEN_MODES = {"sample": 0, "mean": 1, "prior": 2, "given": 3}
 TOPOLOGY = {"tscale": 0, "tref": 1, "sgjoint": 2}
 
@@ -65,6 +65,11 @@ class Batch(C.Structure):
 class LatentReg(C.Structure):
     """snd_latent_reg_t (include/snd_vae.h)."""
     _fields_ = [(k, c_float) for k in ("w_kl", "cap_gamma", "cap_c", "w_dip", "lambda_od", "lambda_d", "w_tc")]
+
+
+class E2ELayer(C.Structure):
+    """snd_e2e_layer_t (include/snd_vae.h)."""
+    _fields_ = [("gamma", vp), ("beta", vp), ("w", vp), ("b", vp), ("cout", c_int)]
 
 
 # name -> (restype, argtypes)
@@ -134,6 +139,10 @@ _SIGS = {
     "snd_bn_relu_fwd": (c_int, [vp, c_ll, c_int, vp, vp, vp, vp]),
     "snd_bn_relu_bwd": (c_int, [vp, vp, c_ll, c_int, vp, vp, vp, vp, vp, vp]),
     "snd_e2e_head_ce": (c_int, [vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "snd_e2e_decode_workspace": (c_size, [c_int, c_int, c_int, C.POINTER(c_int), c_int]),
+    "snd_e2e_decode": (c_int, [vp, c_int, c_int, c_int, c_int, C.POINTER(E2ELayer), c_int, vp, vp, vp, vp, vp, vp,
+                               vp, c_size, vp]),
+    "snd_sigmoid_linear_fwd": (c_int, [vp, c_int, c_ll, c_int, vp, vp, c_int, vp, c_int, vp]),
     "snd_latent_reg_workspace": (c_size, [c_int, c_int]),
     "snd_latent_reg": (c_int, [vp, vp, vp, c_int, c_int, C.POINTER(LatentReg), vp, vp, vp, vp, vp]),
     "snd_bn_act_fwd": (c_int, [vp, c_int, c_ll, c_int, vp, vp, c_int, c_int, vp, c_int, vp]),

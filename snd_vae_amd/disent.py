@@ -2,6 +2,9 @@
 
 * ``e2e`` / ``e2e_bwd``: the structure decoder's edge-to-edge filter
   (`layers.py:431-450`; applied with k_h = N at `model.py:196`), fp32.
+* ``structure_decoder`` / ``structure_decode``: the e2e structure decoder of
+  `model.py:193-208`, with the CE and every gradient (training) or forward only
+  (``snd_e2e_decode``: the generated adjacency for sampling and traversal).
 * ``latent_reg``: one latent group's regulariser (KL, the 'disentangled_C'
   capacity form, DIP, total correlation; `optimizer.py:7-58,159-190`) with its
   gradients, one launch.
@@ -132,6 +135,47 @@ def _bn_relu(y, g, b):
     x = torch.empty_like(y)
     _lib.check(_lib.lib().snd_bn_relu_fwd(_P(y), rows, c, _P(g), _P(b), _P(x), _lib.stream_ptr()), "snd_bn_relu_fwd")
     return x
+
+
+def structure_decode(z, layers, head, want_margin=False):
+    """The generated adjacency of `model.py:193-208` alone: the forward-only decoder
+    ``snd_e2e_decode`` (layer 0 factorised over the pair structure, BN / relu / head /
+    argmax fused; no pair tensor and no logits in device memory).
+
+    z [B, N, D]; ``layers`` / ``head`` as for ``structure_decoder``.  Returns adj uint8
+    [B, N, N] (1 iff logit 1 > logit 0, the diagonal 0), and with ``want_margin`` also the
+    margin l1 - l0 as float32 [B, N, N] (-1 on the diagonal)."""
+    B, N, D = z.shape
+    _f32(z, "structure_decode z")
+    if not layers:
+        raise ValueError("structure_decode: at least one e2e layer")
+    for i, lay in enumerate(layers):
+        for k in ("gamma", "beta", "w", "b"):
+            _f32(lay[k], f"structure_decode layers[{i}][{k!r}]")
+    for k in ("gamma", "beta", "w", "b"):
+        _f32(head[k], f"structure_decode head[{k!r}]")
+    cin = 2 * D
+    for i, lay in enumerate(layers):
+        if tuple(lay["w"].shape[:2]) != (N, cin) or lay["gamma"].numel() != cin or lay["beta"].numel() != cin \
+                or lay["b"].numel() != lay["w"].shape[2]:
+            raise ValueError(f"structure_decode: layer {i} wants gamma/beta [{cin}], w [{N}, {cin}, O], b [O]")
+        cin = lay["w"].shape[2]
+    if tuple(head["w"].shape) != (cin, 2) or head["gamma"].numel() != cin or head["beta"].numel() != cin \
+            or head["b"].numel() != 2:
+        raise ValueError(f"structure_decode: head wants gamma/beta [{cin}], w [{cin}, 2], b [2]")
+    L_ = _lib.lib()
+    n = len(layers)
+    couts = (C.c_int * n)(*[int(lay["w"].shape[2]) for lay in layers])
+    arr = (_lib.E2ELayer * n)(*[_lib.E2ELayer(_P(lay["gamma"]), _P(lay["beta"]), _P(lay["w"]), _P(lay["b"]),
+                                              int(lay["w"].shape[2])) for lay in layers])
+    nbytes = int(L_.snd_e2e_decode_workspace(B, N, D, couts, n))
+    ws = torch.empty(max(nbytes, 16), device=z.device, dtype=torch.uint8)
+    adj = torch.empty(B, N, N, device=z.device, dtype=torch.uint8)
+    margin = torch.empty(B, N, N, device=z.device, dtype=torch.float32) if want_margin else None
+    _lib.check(L_.snd_e2e_decode(_P(z), D, B, N, D, arr, n, _P(head["gamma"]), _P(head["beta"]), _P(head["w"]),
+                                 _P(head["b"]), _P(adj), _P(margin), _P(ws), nbytes, _lib.stream_ptr()),
+               "snd_e2e_decode")
+    return (adj, margin) if want_margin else adj
 
 
 def structure_decoder(z, adj, layers, head):

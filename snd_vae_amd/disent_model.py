@@ -40,7 +40,7 @@ import torch
 from . import _lib
 from .config import CONV_K
 from .data import SGBatch
-from .disent import disentangled_cost, structure_decoder
+from .disent import disentangled_cost, structure_decode, structure_decoder
 from .layers import conv1d_same_bwd, graph_convolution, spmm
 from .params import _glorot_uniform, _truncated_normal
 from .sg import SGGraph, layer_param_shapes, make_layer
@@ -210,7 +210,9 @@ RELU, LRELU, IDENT = 1, 2, 0
 
 class DisentangledSGCNModelVAE:
     """Parameters (one flat fp32 buffer), TF1 Adam state and the training step of the
-    disentangled model for batches of ``n_graphs`` SGBatch graphs on one GPU."""
+    disentangled model for batches of ``n_graphs`` SGBatch graphs on one GPU, and its
+    inference: ``encode``, ``decode`` (any number of graphs), ``generate`` (reconstruction,
+    means, prior samples) and the latent traversals ``traverse`` / ``traverse_all``."""
 
     def __init__(self, cfg: DisentangledConfig, n_graphs: int, blocks: Optional[Dict[str, np.ndarray]] = None,
                  seed: int = 0, device="cuda"):
@@ -235,6 +237,7 @@ class DisentangledSGCNModelVAE:
             avg[b, b * S:(b + 1) * S] = 1.0 / S
         self._avg = torch.from_numpy(avg).to(device)
         self._ones = torch.ones(max(B * S * cfg.n_nodes, 1), device=device)
+        self._avg_cache = {}                                         # decode(): the mean over S' copies
         f = cfg.num_feature
         self.sg_layers = []
         for i, hid in enumerate(cfg.sg_conv_hidden):
@@ -269,17 +272,16 @@ class DisentangledSGCNModelVAE:
         """out[cols] = sum over rows of dy (a 1 x rows by rows x cols GEMM: bias gradients)."""
         _gemm(self._ones, dy, out, 1, cols, rows, ta=True, lda=1, ldb=ld if ld is not None else cols)
 
-    # ---- one training step
-    def step(self, batch: "DeviceDisentBatch", eps: Dict[str, torch.Tensor]) -> Dict[str, float]:
-        """Forward, hand-chained backward and the TF1-Adam update of one batch
-        (main.py:331); eps: {'s': [B, Ls], 'g': [B, Lg], 'sg': [B*S, Lsg]} normals."""
-        cfg, B = self.cfg, self.B
-        N, F, nh, S = cfg.n_nodes, cfg.num_feature, cfg.node_h, cfg.sampling_num
+    # ---- the three encoders (model.py:104-151), shared by step() and encode()
+    def _encoders(self, batch: "DeviceDisentBatch", B: int):
+        """Forward of the graph, spatial and spatial-graph encoders for a batch of B graphs:
+        (graph layers, spatial layers, SG output, heads, widths, (ms_g, ms_s, ms_sg)) with
+        ms = [mu | logstd] per row; everything step()'s backward reads."""
+        cfg = self.cfg
+        N, F, S = cfg.n_nodes, cfg.num_feature, cfg.sampling_num
         R, RS = B * N, B * S * N
         dev = self.device
         T = lambda *shape: torch.empty(*shape, device=dev)
-        self.grads.zero_()
-        # ================================ encoders ================================
         # graph encoder (model.py:104-115)
         x = batch.x
         gl = []
@@ -327,15 +329,34 @@ class DisentangledSGCNModelVAE:
         Vsg = T(RS, Wsg)
         _bn_act(sg_out, Wsg, RS, Wsg, self.w("encoder_sg/gamma"), self.w("encoder_sg/beta"), IDENT, False, Vsg, Wsg)
         ms_sg = head("g_sg", Vsg, B * S, N * Wsg, cfg.sg_hidden, cfg.sg_latent)
+        return gl, sl, sg_out, heads, (Wg, Ws, Wsg), (ms_g, ms_s, ms_sg)
+
+    def _reparam(self, ms, rows, lat, eps):
+        """z = mu + eps e^logstd (model.py:153-161) over ms = [mu | logstd] rows."""
+        zz = torch.empty(rows, lat, device=self.device)
+        kl = torch.zeros(max(1, _lib.lib().snd_reparam_kl_blocks(rows, lat)), dtype=torch.float64,
+                         device=self.device)
+        _lib.check(_lib.lib().snd_reparam_kl(_P(ms), 2 * lat, rows, lat, _P(eps), 0, None, None, _P(zz),
+                                             _P(kl), _lib.stream_ptr()), "snd_reparam_kl")
+        return zz
+
+    # ---- one training step
+    def step(self, batch: "DeviceDisentBatch", eps: Dict[str, torch.Tensor]) -> Dict[str, float]:
+        """Forward, hand-chained backward and the TF1-Adam update of one batch
+        (main.py:331); eps: {'s': [B, Ls], 'g': [B, Lg], 'sg': [B*S, Lsg]} normals."""
+        cfg, B = self.cfg, self.B
+        N, F, nh, S = cfg.n_nodes, cfg.num_feature, cfg.node_h, cfg.sampling_num
+        R, RS = B * N, B * S * N
+        dev = self.device
+        T = lambda *shape: torch.empty(*shape, device=dev)
+        self.grads.zero_()
+        # ================================ encoders ================================
+        gl, sl, sg_out, heads, (Wg, Ws, Wsg), (ms_g, ms_s, ms_sg) = self._encoders(batch, B)
         # get_z (model.py:153-161)
         z = {}
         for name, ms, rows, lat in (("s", ms_s, B, cfg.s_latent), ("g", ms_g, B, cfg.g_latent),
                                     ("sg", ms_sg, B * S, cfg.sg_latent)):
-            zz = T(rows, lat)
-            kl = torch.zeros(max(1, _lib.lib().snd_reparam_kl_blocks(rows, lat)), dtype=torch.float64, device=dev)
-            _lib.check(_lib.lib().snd_reparam_kl(_P(ms), 2 * lat, rows, lat, _P(eps[name]), 0, None, None, _P(zz),
-                                                 _P(kl), _lib.stream_ptr()), "snd_reparam_kl")
-            z[name] = zz
+            z[name] = self._reparam(ms, rows, lat, eps[name])
         # ================================ decoder =================================
         zbar = T(B, cfg.sg_latent)
         _gemm(self._avg, z["sg"], zbar, B, cfg.sg_latent, B * S)
@@ -501,6 +522,225 @@ class DisentangledSGCNModelVAE:
         out = dict(zip(names, overall))
         out["correct"] = correct
         return out
+
+
+    # ---- inference: encode, decode, generate, traverse (model.py:153-358)
+    def _n_graphs(self, batch: "DeviceDisentBatch") -> int:
+        B, rem = divmod(batch.x.numel(), self.cfg.n_nodes * self.cfg.num_feature)
+        if rem or B < 1:
+            raise ValueError("the batch's node features are not [B * n_nodes, num_feature]")
+        return B
+
+    def encode(self, batch: "DeviceDisentBatch", eps: Optional[Dict[str, torch.Tensor]] = None):
+        """The three encoders (the forward half of step()): {'s' | 'g' | 'sg': {'mu', 'logstd'
+        [, 'z']}}, rows [B, L] for s and g and per copy [B * S, Lsg] for sg (``mean_over_copies``
+        averages them, main.py:407).  With eps = {'s': [B, Ls], 'g': [B, Lg], 'sg': [B*S, Lsg]}
+        normals, z = mu + eps e^logstd (get_z, model.py:153-161) is included."""
+        cfg, B = self.cfg, self._n_graphs(batch)
+        ms_g, ms_s, ms_sg = self._encoders(batch, B)[5]
+        out = {}
+        for name, ms, rows, lat in (("s", ms_s, B, cfg.s_latent), ("g", ms_g, B, cfg.g_latent),
+                                    ("sg", ms_sg, B * cfg.sampling_num, cfg.sg_latent)):
+            out[name] = {"mu": ms[:, :lat].contiguous(), "logstd": ms[:, lat:].contiguous()}
+            if eps is not None:
+                e = eps[name]
+                if tuple(e.shape) != (rows, lat) or e.dtype != torch.float32 or not e.is_contiguous():
+                    raise ValueError(f"encode: eps[{name!r}] must be contiguous float32 [{rows}, {lat}]")
+                out[name]["z"] = self._reparam(ms, rows, lat, e)
+        return out
+
+    def _chain(self, inp, R, prefix, bnp, chans, key):
+        """conv1d(k=5, SAME) + BN (no activation) per channel entry (model.py:189-191,214-216)."""
+        N = self.cfg.n_nodes
+        h, cin = inp, inp.shape[1]
+        for i, co in enumerate(chans):
+            y = torch.empty(R, co, device=self.device)
+            _conv(h, cin, R, N, cin, self.w(f"{prefix}{i + key}_deconv/kernel"), co,
+                  self.w(f"{prefix}{i + key}_deconv/bias"), y)
+            u = torch.empty(R, co, device=self.device)
+            _bn_act(y, co, R, co, self.w(f"{bnp}{i}/gamma"), self.w(f"{bnp}{i}/beta"), IDENT, False, u, co)
+            h, cin = u, co
+        return h, cin
+
+    def _sigmoid_linear(self, u, R, cin, wname, cout):
+        y = torch.empty(R, cout, device=self.device)
+        _lib.check(_lib.lib().snd_sigmoid_linear_fwd(_P(u), cin, R, cin, _P(self.w(wname + "/Matrix")),
+                                                     _P(self.w(wname + "/bias")), cout, _P(y), cout,
+                                                     _lib.stream_ptr()), "snd_sigmoid_linear_fwd")
+        return y
+
+    def decode(self, z_s, z_sg, z_g, want_margin: bool = False) -> Dict[str, torch.Tensor]:
+        """decoder(z_s, z_sg, z_g) of model.py:172-222 for any number of graphs B (not tied
+        to the constructor's n_graphs): z_s [B, Ls], z_g [B, Lg], z_sg [B * S', Lsg] with J_sg
+        averaged over the S' copies of a graph (model.py:177-180; S' = 1 for a traversal).
+        Returns generated_adj uint8 [B, N, N] (the forward-only e2e decoder), generated_spatial
+        [B, N, spatial_dim], generated_node_feat [B, N, F], and with want_margin the adjacency
+        margin logit1 - logit0 [B, N, N]."""
+        cfg, dev = self.cfg, self.device
+        N, F, nh = cfg.n_nodes, cfg.num_feature, cfg.node_h
+        for t, lat, name in ((z_s, cfg.s_latent, "z_s"), (z_sg, cfg.sg_latent, "z_sg"), (z_g, cfg.g_latent, "z_g")):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2
+                    and t.shape[1] == lat and t.shape[0] >= 1):
+                raise ValueError(f"decode: {name} must be a contiguous float32 device tensor [rows, {lat}]")
+        B = z_s.shape[0]
+        Sp, rem = divmod(z_sg.shape[0], B)
+        if z_g.shape[0] != B or rem or Sp < 1:
+            raise ValueError(f"decode: z_s [{B}, Ls] needs z_g [{B}, Lg] and z_sg [{B} * S', Lsg], "
+                             f"got {z_g.shape[0]} and {z_sg.shape[0]} rows")
+        R = B * N
+        T = lambda *shape: torch.empty(*shape, device=dev)
+        zbar = z_sg
+        if Sp > 1:                                                    # the mean commutes with d_sg_lin1
+            avg = self._avg_cache.get((B, Sp))
+            if avg is None:
+                a = np.zeros((B, B * Sp), np.float32)
+                for b in range(B):
+                    a[b, b * Sp:(b + 1) * Sp] = 1.0 / Sp
+                avg = self._avg_cache[(B, Sp)] = torch.from_numpy(a).to(dev)
+            zbar = T(B, cfg.sg_latent)
+            _gemm(avg, z_sg, zbar, B, cfg.sg_latent, B * Sp)
+        J = {}
+        for name, zz, lat in (("sg", zbar, cfg.sg_latent), ("s", z_s, cfg.s_latent), ("g", z_g, cfg.g_latent)):
+            j = T(B, N * nh)
+            _gemm(zz, self.w(f"d_{name}_lin1/Matrix"), j, B, N * nh, lat, bias=self.w(f"d_{name}_lin1/bias"))
+            J[name] = j.view(R, nh)
+        Jsg_g, Jsg_s = T(R, 2 * nh), T(R, 2 * nh)                     # [J_sg | J_g], [J_sg | J_s]
+        Jsg_g[:, :nh].copy_(J["sg"]); Jsg_g[:, nh:].copy_(J["g"])
+        Jsg_s[:, :nh].copy_(J["sg"]); Jsg_s[:, nh:].copy_(J["s"])
+        # node features (model.py:186-194)
+        nu, nc = self._chain(Jsg_g, R, "n", "d_bn_n", cfg.n_d_channel, 0)
+        Vn = T(R, nc)
+        _bn_act(nu, nc, R, nc, self.w("decoder_node/gamma"), self.w("decoder_node/beta"), IDENT, False, Vn, nc)
+        node = self._sigmoid_linear(Vn, R, nc, "d_n_lin2", F)
+        # adjacency (model.py:193-208)
+        layers = [{"gamma": self.w(f"d_bn_e{i}/gamma"), "beta": self.w(f"d_bn_e{i}/beta"),
+                   "w": self.w(f"e{i}_deconv/w1"), "b": self.w(f"e{i}_deconv/biases1")}
+                  for i in range(len(cfg.e_d_hidden))]
+        hd = {"gamma": self.w("decoder_adj/gamma"), "beta": self.w("decoder_adj/beta"),
+              "w": self.w("d_e_lin2/Matrix"), "b": self.w("d_e_lin2/bias")}
+        res = structure_decode(Jsg_g.view(B, N, 2 * nh), layers, hd, want_margin=want_margin)
+        # coordinates (model.py:212-219)
+        su, sc = self._chain(Jsg_s, R, "s", "d_bn_s", cfg.s_d_channel, 1)
+        spatial = self._sigmoid_linear(su, R, sc, "d_s_lin2", cfg.spatial_dim)
+        out = {"generated_adj": res[0] if want_margin else res,
+               "generated_spatial": spatial.view(B, N, cfg.spatial_dim),
+               "generated_node_feat": node.view(B, N, F)}
+        if want_margin:
+            out["margin"] = res[1]
+        return out
+
+    def generate(self, batch: "DeviceDisentBatch", z: str = "sample", eps: Optional[Dict[str, torch.Tensor]] = None,
+                 seed: int = 0, want_margin: bool = False) -> Dict[str, torch.Tensor]:
+        """Decode one of three latents of a batch: 'sample' get_z (reconstruction,
+        test_reconstruct), 'mean' the encoder means, 'prior' get_random_z (model.py:163-169,
+        test_generation).  The normals are the caller's eps ({'s': [B, Ls], 'g': [B, Lg],
+        'sg': [B*S, Lsg]}) or drawn from a torch generator seeded with ``seed``.  Returns the
+        decode() outputs plus z_mean_s / z_mean_g / z_mean_sg (main.py:361)."""
+        if z not in ("sample", "mean", "prior"):
+            raise ValueError(f"generate: z must be 'sample', 'mean' or 'prior', got {z!r}")
+        cfg, B = self.cfg, self._n_graphs(batch)
+        if eps is None and z != "mean":
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(int(seed))
+            eps = {k: torch.randn(rows, lat, device=self.device, generator=gen)
+                   for k, rows, lat in (("s", B, cfg.s_latent), ("g", B, cfg.g_latent),
+                                        ("sg", B * cfg.sampling_num, cfg.sg_latent))}
+        enc = self.encode(batch, eps if z == "sample" else None)
+        if z == "prior":
+            for k, rows, lat in (("s", B, cfg.s_latent), ("g", B, cfg.g_latent),
+                                 ("sg", B * cfg.sampling_num, cfg.sg_latent)):
+                if tuple(eps[k].shape) != (rows, lat):
+                    raise ValueError(f"generate: eps[{k!r}] must be [{rows}, {lat}]")
+            lat = {k: eps[k] for k in ("s", "g", "sg")}
+        else:
+            lat = {k: enc[k]["z" if z == "sample" else "mu"] for k in ("s", "g", "sg")}
+        out = self.decode(lat["s"], lat["sg"], lat["g"], want_margin=want_margin)
+        for k in ("s", "g", "sg"):
+            out[f"z_mean_{k}"] = enc[k]["mu"]
+        return out
+
+    def _rows_to_device(self, rows):
+        return [torch.from_numpy(np.ascontiguousarray(r, np.float32)).to(self.device) for r in rows]
+
+    def traverse(self, group: str, dim: int, z_s, z_g, z_sg, values, want_margin: bool = False):
+        """traverse(group_type, fix_dim) of model.py:232-265 without the file I/O: decode the
+        V graphs of ``traverse_rows`` (dimension ``dim`` of ``group`` walks ``values``)."""
+        zs, zg, zsg = self._rows_to_device(traverse_rows(group, dim, z_s, z_g, z_sg, values))
+        return self.decode(zs, zsg, zg, want_margin=want_margin)
+
+    def traverse_all(self, z_s, z_g, z_sg, values, chunk: int = 256, want_margin: bool = False):
+        """traverse_latent of model.py:326-358: decode the (Ls + Lg + Lsg) V graphs of
+        ``traverse_all_rows`` in chunks of at most ``chunk`` graphs (bounded memory) and
+        concatenate them."""
+        if chunk < 1:
+            raise ValueError("traverse_all: chunk must be at least 1")
+        zs, zg, zsg = traverse_all_rows(z_s, z_g, z_sg, values)
+        parts = []
+        for lo in range(0, zs.shape[0], chunk):
+            a, b, c = self._rows_to_device((zs[lo:lo + chunk], zg[lo:lo + chunk], zsg[lo:lo + chunk]))
+            parts.append(self.decode(a, c, b, want_margin=want_margin))
+        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+
+def mean_over_copies(z_sg, sampling_num: int):
+    """[B * S, L] per-copy latents -> [B, L], the mean over a graph's S copies (main.py:407);
+    numpy or torch."""
+    rows = z_sg.shape[0]
+    if sampling_num < 1 or rows % sampling_num:
+        raise ValueError(f"{rows} rows are not a multiple of sampling_num {sampling_num}")
+    return z_sg.reshape(rows // sampling_num, sampling_num, -1).mean(1)
+
+
+def _traverse_args(z_s, z_g, z_sg, values):
+    base = [np.atleast_2d(np.asarray(a, np.float32)) for a in (z_s, z_g, z_sg)]
+    length = sum(a.shape[1] for a in base)
+    M = base[0].shape[0]
+    if any(a.ndim != 2 or a.shape[0] != M for a in base) or M not in (1, length):
+        raise ValueError(f"traverse: base latents need 1 or Ls + Lg + Lsg = {length} rows each")
+    if isinstance(values, dict):
+        vals = [np.asarray(values[k], np.float32).reshape(-1) for k in ("s", "g", "sg")]
+    else:
+        vals = [np.asarray(values, np.float32).reshape(-1)] * 3
+    V = vals[0].size
+    if V < 1 or any(v.size != V for v in vals):
+        raise ValueError("traverse: values needs at least one entry, the same count for every group")
+    return base, vals, length, V
+
+
+def traverse_all_rows(z_s, z_g, z_sg, values):
+    """The latent rows of traverse_latent (model.py:326-358), on the host.
+
+    Base latents z_s [M, Ls], z_g [M, Lg], z_sg [M, Lsg] with M = 1 (one base for every
+    block) or M = Ls + Lg + Lsg (base k for block k, as the reference's saved latents);
+    ``values``: V entries, or {'s' | 'g' | 'sg': V entries} per group.  Block k is V copies
+    of its base with one dimension overwritten by ``values``: blocks 0 .. Ls-1 walk the
+    dimensions of z_s, the next Lg those of z_g, the last Lsg those of z_sg
+    (model.py:339-349).  Returns float32 (z_s, z_g, z_sg) of (Ls + Lg + Lsg) V rows each;
+    one z_sg row per graph (S' = 1)."""
+    base, vals, length, V = _traverse_args(z_s, z_g, z_sg, values)
+    rows = [np.repeat(np.broadcast_to(a, (length, a.shape[1])), V, axis=0).copy() for a in base]
+    k = 0
+    for r, v in zip(rows, vals):
+        for dim in range(r.shape[1]):
+            r[k * V:(k + 1) * V, dim] = v
+            k += 1
+    return tuple(rows)
+
+
+def traverse_rows(group: str, dim: int, z_s, z_g, z_sg, values):
+    """The V rows of one block of ``traverse_all_rows`` (traverse, model.py:232-265):
+    dimension ``dim`` of ``group`` ('s', 'g' or 'sg') walks ``values``, everything else
+    stays at the block's base."""
+    base, vals, length, V = _traverse_args(z_s, z_g, z_sg, values)
+    if group not in ("s", "g", "sg"):
+        raise ValueError(f"traverse: group must be 's', 'g' or 'sg', got {group!r}")
+    gi = ("s", "g", "sg").index(group)
+    if not 0 <= dim < base[gi].shape[1]:
+        raise ValueError(f"traverse: dim {dim} outside group {group!r} of {base[gi].shape[1]} dimensions")
+    k = sum(a.shape[1] for a in base[:gi]) + dim
+    rows = [np.repeat(a[k:k + 1] if a.shape[0] > 1 else a, V, axis=0).copy() for a in base]
+    rows[gi][:, dim] = vals[gi]
+    return tuple(rows)
 
 
 class DeviceDisentBatch:
