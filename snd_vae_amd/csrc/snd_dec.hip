@@ -190,7 +190,8 @@ __device__ __forceinline__ __bf16* img_at(__bf16* img, int row, int kp, int n0) 
 // KCS = kpw / 32 k-chunks per tap as a compile-time count: the tap x chunk loop
 // unrolls whole, so the operand reads of later chunks are issued ahead of the
 // MFMAs of earlier ones (a runtime count left one LDS round trip per chunk exposed)
-template <int NBH, int KCS, class Pre, class Epi>
+// PIN: PRE loads something (see the epilogue's head)
+template <int NBH, int KCS, bool PIN, class Pre, class Epi>
 __device__ __forceinline__ void conv_phase_t(const __bf16* xs, int kpx, const __bf16* ws, int kpw, int np,
                                              int n_out, Pre&& pre, Epi&& epi, int dbg) {
   // the wave index through readfirstlane: the row-block loop and the column-block choice
@@ -219,7 +220,11 @@ __device__ __forceinline__ void conv_phase_t(const __bf16* xs, int kpx, const __
   // (round 5: one HBM round trip per row-block pass was exposed in the backward phases)
   f32x4 ypn[NBH];
   if (k0 < nrb) pre(16 * k0 + li, nb0, ypn);
-  for (int rb = k0; rb < nrb; rb += wpc) {
+  // measurement only (debug bit 1 << 26, results wrong): a phase whose row blocks leave one
+  // block over a whole number of passes (nrb % wpc == 1: the halo's 4 - 8 rows) skips it,
+  // which times that last, nearly empty pass (tools/dec_stamps.py --flags 0,0x4000000)
+  const int nrl = ((kdbg(dbg) & (1 << 26)) && nrb > 1 && nrb % wpc == 1) ? nrb - 1 : nrb;
+  for (int rb = k0; rb < nrl; rb += wpc) {
     f32x4 yp[NBH];
 #pragma unroll
     for (int i = 0; i < NBH; ++i) yp[i] = ypn[i];
@@ -251,6 +256,12 @@ __device__ __forceinline__ void conv_phase_t(const __bf16* xs, int kpx, const __
         }
       }
     }
+    // the next block's operands are taken here, before the epilogue's global stores: waited
+    // for at the loop's head they drained those stores as well (vmcnt counts both), once a pass
+    if constexpr (PIN) {
+#pragma unroll
+      for (int i = 0; i < NBH; ++i) asm volatile("" : "+v"(ypn[i]));
+    }
     epi(16 * rb + li, nb0, acc, yp);
   }
 }
@@ -258,11 +269,11 @@ __device__ __forceinline__ void conv_phase_t(const __bf16* xs, int kpx, const __
 // the unrolled instantiation when kpw / 32 == KX and the runtime loop otherwise (KX 0:
 // always the runtime loop).  One unrolled instantiation per call site keeps the
 // backward chain within 128 VGPRs.
-template <int NBH, int KX, class Pre, class Epi>
+template <int NBH, int KX, bool PIN = false, class Pre, class Epi>
 __device__ __forceinline__ void conv_phase(const __bf16* xs, int kpx, const __bf16* ws, int kpw, int np,
                                            int n_out, Pre&& pre, Epi&& epi, int dbg = 0) {
-  if (KX > 0 && kpw == 32 * KX) conv_phase_t<NBH, KX>(xs, kpx, ws, kpw, np, n_out, pre, epi, dbg);
-  else conv_phase_t<NBH, 0>(xs, kpx, ws, kpw, np, n_out, pre, epi, dbg);
+  if (KX > 0 && kpw == 32 * KX) conv_phase_t<NBH, KX, PIN>(xs, kpx, ws, kpw, np, n_out, pre, epi, dbg);
+  else conv_phase_t<NBH, 0, PIN>(xs, kpx, ws, kpw, np, n_out, pre, epi, dbg);
 }
 
 // The same phase with streamed weights (STR): the weights arrive one tap at a time through two LDS
@@ -348,6 +359,16 @@ __device__ __forceinline__ float colpar(const ColMap& m, int n, const float* A, 
   if (!m.valid(n) || !A) return 0.f;
   if (n < m.a || !Bv) return A[n < m.a ? n : m.logical(n)];
   return Bv[n - m.offb];
+}
+// the same as an address: a column outside the layout or a missing vector reads `zero`
+// (+0, what colpar returns).  The kernels' staging loads every parameter through one of
+// these, unconditionally, so all of them are in flight together and one wait takes them
+// (a load under colpar's branches was waited for before the next was issued)
+__device__ __forceinline__ const float* colpar_at(const ColMap& m, int n, const float* A, const float* Bv,
+                                                  const float* zero) {
+  const bool inA = n < m.a || !Bv;
+  const float* p = inA ? A + (n < m.a ? n : m.logical(n)) : Bv + (n - m.offb);
+  return (m.valid(n) && A) ? p : zero;
 }
 
 // ------------------------------------------------------------------ heads
@@ -472,6 +493,51 @@ dec_fwd_kernel(DecChainFwdArgs a) {
     }
   }
   __syncthreads();
+  // The head parameters, the column parameters of the three convs and the tile's targets:
+  // every thread loads its share through a selected address (`zero` where it has none),
+  // all issued together with the window and weight DMAs below; their first use -- the LDS
+  // stores before wait_dma() -- is the one wait.  (As branches around single loads they were
+  // 13 load-then-wait trips in a row on waves 0 - 1, each draining the DMAs as well.)
+  constexpr int HPT = DTK == 1024 ? 512 : DTK - 128;   // threads [HPT, HPT + 128)
+  static_assert(DTK - 128 >= 2 * TR || DTK == 1024, "dec_fwd: head parameter threads overlap the targets'");
+  const float* zf = reinterpret_cast<const float*>(a.zero);
+  const bool hpt = tid >= HPT && tid < HPT + 128;
+  const int hh = ((tid - HPT) >> 6) & 1, hj = (tid - HPT) & 63;
+  float hv;
+  {
+    const int cin = hh ? 20 : 10, cout = hh ? 1 : 2;
+    const float* w = hh ? a.wn : a.ws;
+    const float* b = hh ? a.bn : a.bs;
+    const float* g = hh ? a.g2n : a.g3;
+    const float* be = hh ? a.be2n : a.be3;
+    const float* src = zf;
+    if (hj < cin * cout) src = w + hj;
+    else if (hj >= 20 && hj < 20 + cout) src = b + (hj - 20);
+    else if (hj >= 24 && hj < 24 + cin) src = g + (hj - 24);
+    else if (hj >= 24 + cin && hj < 24 + 2 * cin) src = be + (hj - 24 - cin);
+    hv = *(hpt ? src : zf);
+  }
+  float tg[2];
+  {
+    const int orow = tid % TR;
+    const long long gr = tl.r0 + orow;
+    const bool ts_ = tid < TR && orow < own, tx_ = tid >= TR && tid < 2 * TR && orow < own;
+    tg[0] = *(ts_ ? a.s_truth + gr * 2 : (tx_ ? a.x_truth + gr : zf));
+    tg[1] = *(ts_ ? a.s_truth + gr * 2 + 1 : zf);
+  }
+  float cv[9];
+  {
+    const int n = tid & 127;
+    const bool c12 = tid < 128, c3 = tid < 16;
+    const ColMap m3{a.s3, 0, a.s3};
+    const float* cpp[9] = {colpar_at(a.m1, n, a.b1, nullptr, zf),  colpar_at(a.m1, n, a.g1, nullptr, zf),
+                           colpar_at(a.m1, n, a.be1, nullptr, zf), colpar_at(a.m2, n, a.b2s, a.b2n, zf),
+                           colpar_at(a.m2, n, a.g2s, a.g2n, zf),   colpar_at(a.m2, n, a.be2s, a.be2n, zf),
+                           colpar_at(m3, n, a.b3, nullptr, zf),    colpar_at(m3, n, a.g3, nullptr, zf),
+                           colpar_at(m3, n, a.be3, nullptr, zf)};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cv[k] = *((k < 6 ? c12 : c3) ? cpp[k] : zf);
+  }
   // J window [r0 - 6, r0 + own + 6) and the conv1 weights
   if (!(kdbg(a.dbg) & 16))
     stage_window<NWV>(a.zb, a.ldz, a.dj, tl.r0 - 6, in_rows(TR + 8), own + 12, tl.glo, tl.ghi, a.k1.kp,
@@ -481,45 +547,23 @@ dec_fwd_kernel(DecChainFwdArgs a) {
   char* tb1 = tb0 + L.tapb;
   if constexpr (STR) stage_tap_async<NWV>(a.k1, 0, tb0, kdbg(a.dbg));
   else stage_weights(a.k1, reinterpret_cast<char*>(wimg), kdbg(a.dbg));
-  // head parameters and the tile's targets, fetched now so their latency hides under the convs
-  constexpr int HPT = DTK == 1024 ? 512 : DTK - 128;   // threads [HPT, HPT + 128)
-  static_assert(DTK - 128 >= 2 * TR || DTK == 1024, "dec_fwd: head parameter threads overlap the targets'");
-  if (tid >= HPT && tid < HPT + 128) {
-    const int i = tid - HPT, hh = i >> 6, j = i & 63;
-    const int cin = hh ? 20 : 10, cout = hh ? 1 : 2;
-    const float* w = hh ? a.wn : a.ws;
-    const float* b = hh ? a.bn : a.bs;
-    const float* g = hh ? a.g2n : a.g3;
-    const float* be = hh ? a.be2n : a.be3;
-    float v = 0.f;
-    if (j < cin * cout) v = w[j];
-    else if (j >= 20 && j < 20 + cout) v = b[j - 20];
-    else if (j >= 24 && j < 24 + cin) v = g[j - 24];
-    else if (j >= 24 + cin && j < 24 + 2 * cin) v = be[j - 24 - cin];
-    hp[hh][j] = v;
-  }
-  float tg[2] = {0.f, 0.f};
-  if (tid < 2 * TR) {
-    const int orow = tid % TR;
-    const long long gr = tl.r0 + orow;
-    if (orow < own) {
-      if (tid < TR) { tg[0] = a.s_truth[gr * 2]; tg[1] = a.s_truth[gr * 2 + 1]; }
-      else tg[0] = a.x_truth[gr];
-    }
-  }
+  // keep the loads above the DMAs and out of the branches below
+#pragma unroll
+  for (int k = 0; k < 9; ++k) asm volatile("" : "+v"(cv[k]));
+  asm volatile("" : "+v"(hv), "+v"(tg[0]), "+v"(tg[1]));
+  if (hpt) hp[hh][hj] = hv;
   if (tid < 128) {
     const int n = tid;
-    cp1[0][n] = colpar(a.m1, n, a.b1, nullptr);
-    cp1[1][n] = colpar(a.m1, n, a.g1, nullptr) * kBnC;
-    cp1[2][n] = colpar(a.m1, n, a.be1, nullptr);
-    cp2[0][n] = colpar(a.m2, n, a.b2s, a.b2n);
-    cp2[1][n] = colpar(a.m2, n, a.g2s, a.g2n) * kBnC;
-    cp2[2][n] = colpar(a.m2, n, a.be2s, a.be2n);
+    cp1[0][n] = cv[0];
+    cp1[1][n] = cv[1] * kBnC;
+    cp1[2][n] = cv[2];
+    cp2[0][n] = cv[3];
+    cp2[1][n] = cv[4] * kBnC;
+    cp2[2][n] = cv[5];
     if (n < 16) {
-      const ColMap m3{a.s3, 0, a.s3};
-      cp3[0][n] = colpar(m3, n, a.b3, nullptr);
-      cp3[1][n] = colpar(m3, n, a.g3, nullptr) * kBnC;
-      cp3[2][n] = colpar(m3, n, a.be3, nullptr);
+      cp3[0][n] = cv[6];
+      cp3[1][n] = cv[7] * kBnC;
+      cp3[2][n] = cv[8];
     }
   }
   wait_dma();
@@ -752,19 +796,36 @@ dec_bwd_kernel(DecChainBwdArgs a) {
   char* tb1 = tb0 + L.tapb;
   if constexpr (STR) stage_tap_async<NWV>(a.k3t, 0, tb0, kdbg(a.dbg));
   else stage_weights(a.k3t, reinterpret_cast<char*>(wimg3), kdbg(a.dbg));
-  if (tid < 128) {
-    const int n = tid;
-    const ColMap ms{a.m2.a, 0, a.m2.a};
-    cpa[0][n] = colpar(ms, n, a.g2s, nullptr) * kBnC;
-    cpa[1][n] = colpar(ms, n, a.be2s, nullptr);
-    cpb[0][n] = colpar(a.m1, n, a.g1, nullptr) * kBnC;
-    cpb[1][n] = colpar(a.m1, n, a.be1, nullptr);
-  }
-  // dY2 n part of the window [r0 - 4, r0 + own + 4) (the heads' output) into the dY2 image
+  // The column parameters and the dY2 n part of the window [r0 - 4, r0 + own + 4) (the heads'
+  // output, into the dY2 image): every load through a selected address (`zero` where the
+  // thread has none), all in flight together with the DMAs above; the LDS stores before
+  // wait_dma() are their one wait (dec_fwd_kernel's staging).  The n part is at most
+  // (TR + 8) rows x 5 column groups: one item per thread, the loop takes what is left.
   {
+    const float* zf = reinterpret_cast<const float*>(a.zero);
+    const int n = tid & 127;
+    const bool c = tid < 128;
+    const ColMap ms{a.m2.a, 0, a.m2.a};
+    float cv[4] = {*(c ? colpar_at(ms, n, a.g2s, nullptr, zf) : zf), *(c ? colpar_at(ms, n, a.be2s, nullptr, zf) : zf),
+                   *(c ? colpar_at(a.m1, n, a.g1, nullptr, zf) : zf), *(c ? colpar_at(a.m1, n, a.be1, nullptr, zf) : zf)};
     const int wr0 = tl.r0 - 4, nv = own + 8, kp2 = a.k2t.kp;
     const int nq = (a.m2.b + 3) / 4;             // 4-column groups of the n part
-    for (int i = tid; i < ((kdbg(a.dbg) & 16) ? 0 : nv * nq); i += DTK) {
+    const int nit = (kdbg(a.dbg) & 16) ? 0 : nv * nq;
+    const int row0 = tid / nq, q0 = tid - row0 * nq, gr0 = wr0 + row0;
+    const bool v0 = tid < nit && gr0 >= tl.glo && gr0 < tl.ghi;
+    const int n00 = a.m2.offb + 4 * q0;
+    bf16x4 d0 = *reinterpret_cast<const bf16x4*>(v0 ? (const void*)(a.dy2 + (long long)gr0 * a.lddy2 + n00) : a.zero);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(cv[k]));
+    asm volatile("" : "+v"(d0));
+    if (c) {
+      cpa[0][n] = cv[0] * kBnC;
+      cpa[1][n] = cv[1];
+      cpb[0][n] = cv[2] * kBnC;
+      cpb[1][n] = cv[3];
+    }
+    if (v0) *reinterpret_cast<bf16x4*>(img_at(d2, row0, kp2, n00)) = d0;
+    for (int i = tid + DTK; i < nit; i += DTK) {
       const int row = i / nq, q = i - row * nq;
       const int gr = wr0 + row;
       if (gr < tl.glo || gr >= tl.ghi) continue;
@@ -782,21 +843,24 @@ dec_bwd_kernel(DecChainBwdArgs a) {
     const int nbc = a.k3t.np >> 4, ncg = nbc, wpc = NWV / ncg;
     const int nb0 = w % ncg;
     float q[3][1][4] = {};
+    // One 16-byte load per quad through a selected address: a quad that starts inside the s
+    // part lies inside the row (N <= ldy2, both quads' multiples), anything else reads
+    // `zero`.  The columns of a quad past N (the gap, the n part) are dropped in the
+    // epilogue, so nothing here waits for the load before the MFMAs.
     auto pre3t = [&](int orow, int nb, f32x4 (&yp)[1]) {
-                    yp[0] = f32x4{0.f, 0.f, 0.f, 0.f};
                     const int gr = wr0 + orow;
-                    if (orow < n_out && gr >= tl.glo && gr < tl.ghi) {
-                      const int n0 = 16 * nb + 4 * lg;
-                      const float* p = a.y2 + (long long)gr * a.ldy2 + n0;
-#pragma unroll
-                      for (int e = 0; e < 4; ++e) if (n0 + e < N) yp[0][e] = p[e];
-                    }
+                    const int n0 = 16 * nb + 4 * lg;
+                    const bool ok = orow < n_out && gr >= tl.glo && gr < tl.ghi && n0 < N;
+                    yp[0] = *reinterpret_cast<const f32x4*>(ok ? (const void*)(a.y2 + (long long)gr * a.ldy2 + n0) : a.zero);
                   };
-    auto epi3t = [&](int orow, int nb, f32x4 (&acc)[1], f32x4 (&yp)[1]) {
+    auto epi3t = [&](int orow, int nb, f32x4 (&acc)[1], f32x4 (&ypr)[1]) {
       if (orow >= n_out) return;
       const int gr = wr0 + orow;
       const bool ing = gr >= tl.glo && gr < tl.ghi, mine = gr >= tl.r0 && gr < tl.rend;
       const int n0 = 16 * nb + 4 * lg;
+      f32x4 yp[1];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) yp[0][e] = n0 + e < N ? ypr[0][e] : 0.f;
       // columns >= N: zero weights, gamma and beta, so dt = +0 there without a mask
       const f32x4 ga = *reinterpret_cast<const f32x4*>(&cpa[0][n0]);
       const f32x4 be = *reinterpret_cast<const f32x4*>(&cpa[1][n0]);
@@ -822,7 +886,7 @@ dec_bwd_kernel(DecChainBwdArgs a) {
     };
     if constexpr (STR)
       conv_phase_str<1, 1, NWV, 2>(d3, a.k3t.kp, a.k3t, tb0, tb1, 0, &a.k2t, n_out, pre3t, epi3t, a.dbg);
-    else conv_phase<1, 1>(d3, a.k3t.kp, wimg3, a.k3t.kp, a.k3t.np, n_out, pre3t, epi3t, a.dbg);
+    else conv_phase<1, 1, true>(d3, a.k3t.kp, wimg3, a.k3t.kp, a.k3t.np, n_out, pre3t, epi3t, a.dbg);
     if (w / ncg < wpc) colpart_flush<1>(q, slots, a.k3t.np, nb0, nbc, w / ncg);
     __syncthreads();
     for (int i = tid; i < 3 * N; i += DTK) {
@@ -845,14 +909,14 @@ dec_bwd_kernel(DecChainBwdArgs a) {
     const int nbc = a.k2t.np >> 4, ncg = (nbc + 1) / 2, wpc = NWV / ncg;
     const int nb0 = 2 * (w % ncg);
     float q[3][2][4] = {};
-    auto pre2t = [&](int orow, int nb, f32x4 (&yp)[2]) {
+    auto pre2t = [&](int orow, int nb, f32x4 (&yp)[2]) {   // both loads through a selected address: one group
                     const int gr = wr0 + orow;
                     const bool ok = orow < n_out && gr >= tl.glo && gr < tl.ghi;
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {   // Y1's gap / pad columns hold +0 (np = ld1)
-                      yp[i] = f32x4{0.f, 0.f, 0.f, 0.f};
                       const int n0 = 16 * (nb + i) + 4 * lg;
-                      if (ok && nb + i < nbc) yp[i] = *reinterpret_cast<const f32x4*>(a.y1 + (long long)gr * a.ldy1 + n0);
+                      yp[i] = *reinterpret_cast<const f32x4*>(
+                          (ok && nb + i < nbc) ? (const void*)(a.y1 + (long long)gr * a.ldy1 + n0) : a.zero);
                     }
                   };
     auto epi2t = [&](int orow, int nb, f32x4 (&acc)[2], f32x4 (&yp)[2]) {
@@ -882,7 +946,7 @@ dec_bwd_kernel(DecChainBwdArgs a) {
     };
     if constexpr (STR)
       conv_phase_str<2, 2, NWV, 3>(d2, a.k2t.kp, a.k2t, tb0, tb1, 5, &a.k1t, n_out, pre2t, epi2t, a.dbg);
-    else conv_phase<2, 2>(d2, a.k2t.kp, wimg, a.k2t.kp, a.k2t.np, n_out, pre2t, epi2t, a.dbg);
+    else conv_phase<2, 2, true>(d2, a.k2t.kp, wimg, a.k2t.kp, a.k2t.np, n_out, pre2t, epi2t, a.dbg);
     __syncthreads();   // slots: the conv3^T partials were consumed above
     if (w / ncg < wpc) colpart_flush<2>(q, slots, a.k2t.np, nb0, nbc, w / ncg);
     __syncthreads();
