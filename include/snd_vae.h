@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 22
+#define SND_ABI_VERSION 23
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -563,6 +563,48 @@ int snd_e2e_decode(const float* z, int ldz, int n_graphs, int n, int d,
  * yhat [rows, cout] (stride ldy). */
 int snd_sigmoid_linear_fwd(const float* u, int ldu, long long rows, int cin, const float* w,
                            const float* b, int cout, float* yhat, int ldy, snd_stream_t stream);
+
+/* ---- the disentangled step's loss tail and edge-score evaluation (ABI 23) -------
+ * snd_disent_losses: the loss terms of one step of the disentangled model
+ * (optimizer.py:146-203) from the partial results its ops leave on the device, so a step
+ * reads nothing back and can be captured in a graph.
+ * losses[8] (device double) = {cost, spatial_cost, adj_cost, node_cost, kl_g, kl_s, kl_sg, correct}
+ * (optimizer.py:201 order, then main.py:334's count).
+ *   node_cost    = (sum of sse_node[0..node_blocks)) / node_count   (snd_sigmoid_mse's sse)
+ *   spatial_cost = likewise
+ *   adj_cost     = ce_out[0] / pair_count;  correct = ce_out[1]     (snd_e2e_head_ce's out)
+ *   cost = adj_cost + node_cost + spatial_cost + (term_s + term_g + term_sg), terms added in
+ *   that order from 0.0 (reg_x[1] of snd_latent_reg's out[4]; kl_x = reg_x[0]).
+ * reg_s / reg_g may be NULL ('base': their kl is written as 0 and their terms do not enter).
+ * The partials are summed in index order, in double, by one thread: no atomics, no
+ * allocation, no host synchronisation.  SND_ERR_ARG: a NULL sse_node, sse_spatial, ce_out,
+ * reg_sg or losses, a block count < 1, a count <= 0 (or NaN). */
+int snd_disent_losses(const double* sse_node, int node_blocks, double node_count,
+                      const double* sse_spatial, int spatial_blocks, double spatial_count,
+                      const double* ce_out, double pair_count,
+                      const double* reg_s, const double* reg_g, const double* reg_sg,
+                      double* losses, snd_stream_t stream);
+
+/* snd_margin_eval: snd_zzt_eval's counters for the e2e structure decoder, whose edge score
+ * is the margin l1 - l0 that snd_e2e_decode writes (main.py:13-14,423,467 for the
+ * disentangled model).  margin and adj [B, N, N] contiguous fp32; the label is adj != 0.
+ * The N diagonal pairs are skipped by index, whatever they hold (the decoder writes -1
+ * there), and counted as TN.  Per graph b over the N^2 - N off-diagonal pairs:
+ *   hist[b][label][clamp(floor(64 m) + 1024, 0, 2047)] += 1   (int64 [B, 2, 2048],
+ *     snd_zzt_eval's bins; the clamp is done in float, so -inf / +inf land in bins 0 / 2047)
+ *   counts[b] = {TP, FP, FN, TN} (int64 [B, 4]) at the rule m > 0: snd_e2e_decode's adj
+ *     (a tie is 0), so TP + FP is the number of ones of that adj.
+ * NaN margins are unspecified (no fault, no write outside the outputs).  accumulate = 0
+ * clears hist and counts on the stream first, != 0 adds to them.  Integer sums only: the
+ * result does not depend on scheduling and is additive over batches.  No allocation and
+ * no host synchronisation.  Any pointer alignment (16-byte loads where a graph's chunk is
+ * aligned, scalar loads otherwise).  workspace: snd_margin_eval_workspace() bytes (0 today;
+ * NULL is accepted then).  SND_ERR_ARG before anything is launched: a NULL margin, adj,
+ * hist or counts, n_graphs < 1, n < 1, a short workspace. */
+size_t snd_margin_eval_workspace(int n_graphs, int n);
+int snd_margin_eval(const float* margin, const float* adj, int n_graphs, int n,
+                    long long* hist, long long* counts, int accumulate,
+                    void* workspace, size_t workspace_bytes, snd_stream_t stream);
 
 /* ---- a14: the whole train step (main.py:315-334) ---------------------------
  * A plan fixes shapes; the step runs forward + backward of the SND-VAE

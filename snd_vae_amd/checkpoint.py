@@ -5,7 +5,8 @@ and restores them for the test modes.  Here trainable state is the flat fp32
 parameter buffer and TF1-Adam's m / v of the same layout (`params.py`), plus
 the global step; one safetensors file holds them, with the config and the
 block table in the metadata so a restore into a different architecture fails
-loudly instead of silently mis-slicing.
+loudly instead of silently mis-slicing.  The disentangled model
+(`disent_model.py`) is saved the same way, marked as such in the metadata.
 """
 from __future__ import annotations
 
@@ -19,20 +20,31 @@ import torch
 from .config import SNDConfig
 
 
+DISENT = "disentangled"    # metadata "model" of a DisentangledSGCNModelVAE file (absent: SGCNModelVAE)
+
+
 def _meta(model) -> dict:
-    lay = model.layout
+    if isinstance(model.cfg, SNDConfig):
+        lay = model.layout
+        blocks = [[k, int(lay.offsets[k]), int(lay.numel(k))] for k in lay.shapes]
+        kind = {}
+    else:                      # disent_model.DisentangledSGCNModelVAE: its own block table
+        blocks = [[k, int(model.offsets[k]), int(np.prod(s))] for k, s in model.shapes.items()]
+        kind = {"model": DISENT}
     return {
         "format": "snd_vae_amd/1",
         "config": json.dumps(dataclasses.asdict(model.cfg)),
-        "blocks": json.dumps([[k, int(lay.offsets[k]), int(lay.numel(k))] for k in lay.shapes]),
+        "blocks": json.dumps(blocks),
         "param_count": str(model.param_count),
+        **kind,
     }
 
 
-def save(path: str, model, optimizer=None) -> None:
-    """Write params (+ Adam m, v, global step when ``optimizer`` is given).  With a
-    bucketed data-parallel optimizer whose large buckets keep sharded Adam moments,
-    call ``optimizer.sync_state()`` on every rank first (a collective)."""
+def save(path: str, model, optimizer=None, epoch: Optional[int] = None) -> None:
+    """Write params (+ Adam m, v, global step when ``optimizer`` is given, + the epoch when
+    given).  With a bucketed data-parallel optimizer whose large buckets keep sharded Adam
+    moments, call ``optimizer.sync_state()`` on every rank first (a collective).  The
+    disentangled model keeps its own Adam state: pass it as ``optimizer`` too."""
     from safetensors.torch import save_file
     pc = model.param_count
     t = {"params": model.params[:pc].detach().cpu().contiguous()}
@@ -40,17 +52,43 @@ def save(path: str, model, optimizer=None) -> None:
         t["adam_m"] = optimizer.m[:pc].detach().cpu().contiguous()
         t["adam_v"] = optimizer.v[:pc].detach().cpu().contiguous()
         t["global_step"] = optimizer.step_counter.detach().cpu().to(torch.int64).contiguous()
+    if epoch is not None:
+        t["epoch"] = torch.tensor([int(epoch)], dtype=torch.int64)
     save_file(t, path, metadata=_meta(model))
+
+
+def _tuples(d: dict) -> dict:
+    for k, v in d.items():
+        if isinstance(v, list):
+            d[k] = tuple(tuple(e) if isinstance(e, list) else e for e in v)
+    return d
 
 
 def read_config(path: str) -> SNDConfig:
     from safetensors import safe_open
     with safe_open(path, framework="pt") as f:
-        d = json.loads(f.metadata()["config"])
-    for k, v in d.items():
-        if isinstance(v, list):
-            d[k] = tuple(tuple(e) if isinstance(e, list) else e for e in v)
-    return SNDConfig(**d)
+        meta = f.metadata()
+    if meta.get("model") is not None:
+        raise ValueError(f"{path}: a {meta['model']}-model checkpoint (read_disent_config)")
+    return SNDConfig(**_tuples(json.loads(meta["config"])))
+
+
+def read_disent_config(path: str):
+    """The DisentangledConfig a disentangled-model checkpoint was written under."""
+    from safetensors import safe_open
+    from .disent_model import DisentangledConfig
+    with safe_open(path, framework="pt") as f:
+        meta = f.metadata()
+    if meta.get("model") != DISENT:
+        raise ValueError(f"{path}: not a disentangled-model checkpoint")
+    return DisentangledConfig(**_tuples(json.loads(meta["config"])))
+
+
+def read_epoch(path: str) -> Optional[int]:
+    """The epoch ``save(..., epoch=)`` recorded (None when it recorded none)."""
+    from safetensors import safe_open
+    with safe_open(path, framework="pt") as f:
+        return int(f.get_tensor("epoch")[0]) if "epoch" in f.keys() else None
 
 
 def restore(path: str, model, optimizer=None, strict_config: bool = True) -> Optional[int]:
@@ -61,6 +99,9 @@ def restore(path: str, model, optimizer=None, strict_config: bool = True) -> Opt
         if meta.get("format") != "snd_vae_amd/1":
             raise ValueError(f"{path}: not an snd_vae_amd checkpoint")
         want = _meta(model)
+        if meta.get("model") != want.get("model"):
+            raise ValueError(f"{path}: a checkpoint of the {meta.get('model') or 'node-latent'} model, "
+                             f"not of the {want.get('model') or 'node-latent'} model")
         if meta["blocks"] != want["blocks"]:
             raise ValueError(f"{path}: parameter layout differs from the model's")
         if strict_config and meta["config"] != want["config"]:

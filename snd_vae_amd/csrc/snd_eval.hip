@@ -13,14 +13,6 @@
 
 namespace snd {
 
-// The cell of a logit: label * 2048 + clamp(floor(64 L) + 1024, 0, 2047).  The clamp is
-// done in float and once more on the integer, so no input (non-finite z is unspecified, but
-// must not fault) can address outside the histogram.
-__device__ __forceinline__ unsigned eval_key(float L, unsigned label) {
-  const float t = __builtin_amdgcn_fmed3f(floorf(L * 64.f) + 1024.f, 0.f, 2047.f);
-  return (label << 11) | min((unsigned)t, (unsigned)kEvalBins - 1u);
-}
-
 // One increment per lane of the wave.  Logits cluster (an untrained decoder puts every pair
 // near 0, a confident one puts most non-edges into the underflow bin), and LDS atomics of one
 // instruction to one address serialise, so the wave votes first: when half of it or more

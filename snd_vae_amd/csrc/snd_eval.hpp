@@ -19,6 +19,15 @@ namespace snd {
 // order the workgroups finish in: two runs on the same operands are bitwise equal.
 constexpr int kEvalBins = 2048;
 
+// The cell of a score (a zz^T logit, or the e2e decoder's margin in snd_margin_eval):
+// label * 2048 + clamp(floor(64 L) + 1024, 0, 2047).  The clamp is done in float and once
+// more on the integer, so no input (non-finite scores are unspecified, but must not fault)
+// can address outside the histogram.
+__device__ __forceinline__ unsigned eval_key(float L, unsigned label) {
+  const float t = __builtin_amdgcn_fmed3f(floorf(L * 64.f) + 1024.f, 0.f, 2047.f);
+  return (label << 11) | min((unsigned)t, (unsigned)kEvalBins - 1u);
+}
+
 struct ZztEvalArgs {
   const float* z; int ldz; int d;      // [B*n, ldz] fp32 decoder input J, 1 <= d <= 128
   int n, ngraphs;

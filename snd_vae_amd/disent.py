@@ -66,10 +66,12 @@ def e2e_bwd(x, w1, dout):
 
 
 def latent_reg(mu, logstd, z=None, w_kl=1.0, cap_gamma=0.0, cap_c=0.0, w_dip=0.0, lambda_od=10.0,
-               lambda_d=100.0, w_tc=0.0) -> Tuple[Dict[str, float], torch.Tensor, torch.Tensor]:
+               lambda_d=100.0, w_tc=0.0, device_out=False) -> Tuple[Dict[str, float], torch.Tensor, torch.Tensor]:
     """One group's term w_kl kl (or cap_gamma relu(kl - cap_c)) + w_dip DIP(mu) + w_tc TC(z);
     returns ({kl, term, dip, tc}, d term / d mu, d term / d logstd) -- the gradients include
-    the path through z = mu + eps e^logstd (model.py:155-159)."""
+    the path through z = mu + eps e^logstd (model.py:155-159).  ``device_out``: the first
+    entry is snd_latent_reg's out[4] = {kl, term, dip, tc} left on the device (float64), with
+    no host synchronisation."""
     _f32(mu, "latent_reg mu")
     _f32(logstd, "latent_reg logstd")
     if z is not None:
@@ -87,6 +89,8 @@ def latent_reg(mu, logstd, z=None, w_kl=1.0, cap_gamma=0.0, cap_c=0.0, w_dip=0.0
     _lib.check(L_.snd_latent_reg(_P(mu), _P(logstd), _P(z) if z is not None else None, B, L, C.byref(w),
                                  _P(dmu), _P(ds), _P(out), _P(ws) if ws is not None else None,
                                  _lib.stream_ptr()), "snd_latent_reg")
+    if device_out:
+        return out, dmu, ds
     v = out.cpu().tolist()
     return {"kl": v[0], "term": v[1], "dip": v[2], "tc": v[3]}, dmu, ds
 
@@ -178,7 +182,7 @@ def structure_decode(z, layers, head, want_margin=False):
     return (adj, margin) if want_margin else adj
 
 
-def structure_decoder(z, adj, layers, head):
+def structure_decoder(z, adj, layers, head, device_out=False):
     """The e2e structure decoder of `model.py:193-208` with the CE of `optimizer.py:142-144`,
     forward and backward in one call.
 
@@ -186,7 +190,9 @@ def structure_decoder(z, adj, layers, head):
     {gamma, beta (d_bn_e[i], over its input channels), w [N, Cin, Cout], b [Cout]};
     head: {gamma, beta (decoder_adj), w [Cin, 2], b [2]} (d_e_lin2).  Returns
     (adj_cost = mean CE over B N^2, correct = #(argmax == A) (main.py:334), dz,
-    grads: a list of per-layer dicts and the head dict, same keys as the inputs)."""
+    grads: a list of per-layer dicts and the head dict, same keys as the inputs).
+    ``device_out``: instead of the first two entries, snd_e2e_head_ce's out[2] = {CE summed
+    over B N^2, correct} left on the device (float64), with no host synchronisation."""
     B, N, D = z.shape
     _f32(z, "structure_decoder z")
     _f32(adj, "structure_decoder adj")
@@ -232,5 +238,7 @@ def structure_decoder(z, adj, layers, head):
             _lib.check(L_.snd_e2e_pair_bwd(_P(dx), _P(z), B, N, D, _P(l0["gamma"]), _P(l0["beta"]), _P(dz),
                                            _P(grads[0]["gamma"]), _P(grads[0]["beta"]), _P(ws), sp),
                        "snd_e2e_pair_bwd")
+    if device_out:
+        return out, dz, grads, hg
     o = out.cpu().tolist()
     return o[0] / (B * N * N), o[1], dz, grads, hg

@@ -40,7 +40,7 @@ import torch
 from . import _lib
 from .config import CONV_K
 from .data import SGBatch
-from .disent import disentangled_cost, structure_decode, structure_decoder
+from .disent import group_weights, latent_reg, structure_decode, structure_decoder
 from .layers import conv1d_same_bwd, graph_convolution, spmm
 from .params import _glorot_uniform, _truncated_normal
 from .sg import SGGraph, layer_param_shapes, make_layer
@@ -207,6 +207,10 @@ def _conv(x, ldx, rows, npg, cin, w, cout, bias, out):
 
 RELU, LRELU, IDENT = 1, 2, 0
 
+# DisentangledSGCNModelVAE.losses (snd_disent_losses): optimizer.py:201's overall_loss, then
+# main.py:334's count of correct adjacency entries
+LOSS_NAMES = ("cost", "spatial_cost", "adj_cost", "node_cost", "kl_g", "kl_s", "kl_sg", "correct")
+
 
 class DisentangledSGCNModelVAE:
     """Parameters (one flat fp32 buffer), TF1 Adam state and the training step of the
@@ -230,6 +234,7 @@ class DisentangledSGCNModelVAE:
         self.m = torch.zeros(off, device=device)
         self.v = torch.zeros(off, device=device)
         self.step_counter = torch.zeros(1, dtype=torch.int32, device=device)
+        self.losses = torch.zeros(len(LOSS_NAMES), dtype=torch.float64, device=device)   # step_device()
         self.load_blocks(blocks if blocks is not None else init_blocks(cfg, seed))
         S, B = cfg.sampling_num, n_graphs
         avg = np.zeros((B, B * S), np.float32)                   # zbar = avg @ z_sg (model.py:180)
@@ -343,7 +348,46 @@ class DisentangledSGCNModelVAE:
     # ---- one training step
     def step(self, batch: "DeviceDisentBatch", eps: Dict[str, torch.Tensor]) -> Dict[str, float]:
         """Forward, hand-chained backward and the TF1-Adam update of one batch
-        (main.py:331); eps: {'s': [B, Ls], 'g': [B, Lg], 'sg': [B*S, Lsg]} normals."""
+        (main.py:331); eps: {'s': [B, Ls], 'g': [B, Lg], 'sg': [B*S, Lsg]} normals.
+        Returns the loss terms, read back from the device."""
+        cfg, B = self.cfg, self.B
+        (sse_n, n_count), (sse_s, s_count), ce, regs = self._step(batch, eps, cfg.capacity)
+        node_cost = float(sse_n.sum().item()) / n_count
+        o = ce.cpu().tolist()
+        adj_cost, correct = o[0] / (B * cfg.n_nodes * cfg.n_nodes), o[1]
+        spatial_cost = float(sse_s.sum().item()) / s_count
+        reg, kls = 0.0, {}                                            # disent.disentangled_cost
+        for name, r in regs.items():
+            v = r.cpu().tolist()
+            reg += v[1]
+            kls[name] = v[0]
+        cost = adj_cost + node_cost + spatial_cost + reg
+        out = {"cost": cost, "spatial_cost": spatial_cost, "adj_cost": adj_cost, "node_cost": node_cost}
+        if cfg.model_type != "base":                                  # overall_loss order
+            out["kl_g"], out["kl_s"] = kls["g"], kls["s"]
+        out["kl_sg"] = kls["sg"]
+        out["correct"] = correct
+        return out
+
+    def step_device(self, batch: "DeviceDisentBatch", eps: Dict[str, torch.Tensor],
+                    capacity: Optional[float] = None) -> None:
+        """step() without a host synchronisation: the same launches in the same order, then
+        snd_disent_losses writes ``self.losses`` (float64 [8], LOSS_NAMES: kl_g / kl_s are 0
+        for 'base').  Nothing is read back, so the call can be captured in a HIP graph (after
+        one eager call, which sizes the layers' workspaces).  capacity: C of
+        'disentangled_C' for this step (None: cfg.capacity)."""
+        cfg, B = self.cfg, self.B
+        cap = cfg.capacity if capacity is None else float(capacity)
+        (sse_n, n_count), (sse_s, s_count), ce, regs = self._step(batch, eps, cap)
+        _lib.check(_lib.lib().snd_disent_losses(
+            _P(sse_n), sse_n.numel(), float(n_count), _P(sse_s), sse_s.numel(), float(s_count), _P(ce),
+            float(B * cfg.n_nodes * cfg.n_nodes), _P(regs.get("s")), _P(regs.get("g")), _P(regs["sg"]),
+            _P(self.losses), _lib.stream_ptr()), "snd_disent_losses")
+
+    def _step(self, batch: "DeviceDisentBatch", eps: Dict[str, torch.Tensor], cap: float):
+        """The launches of one step, shared by step() and step_device().  Returns what the loss
+        terms are made of, on the device: (sse partials, count) of the node and of the spatial
+        head, snd_e2e_head_ce's {CE sum, correct} and snd_latent_reg's out[4] per group."""
         cfg, B = self.cfg, self.B
         N, F, nh, S = cfg.n_nodes, cfg.num_feature, cfg.node_h, cfg.sampling_num
         R, RS = B * N, B * S * N
@@ -392,19 +436,20 @@ class DisentangledSGCNModelVAE:
                                                   _P(yhat), _P(du), cin, _P(self.g(wname + "/Matrix")),
                                                   _P(self.g(wname + "/bias")), _P(ws), ws.numel() * 4,
                                                   _lib.stream_ptr()), "snd_sigmoid_mse")
-            return float(sse.sum().item()) / (R * cout), du
+            return (sse, R * cout), du
         # node decoder (model.py:186-191): conv + BN (no activation) x2, BN decoder_node, sigmoid head
         nlay, nu, nc = conv_bn_chain(Jsg_g, "n", "d_bn_n", cfg.n_d_channel, 0)
         Vn = T(R, nc)
         _bn_act(nu, nc, R, nc, self.w("decoder_node/gamma"), self.w("decoder_node/beta"), IDENT, False, Vn, nc)
-        node_cost, dVn = sigmoid_head(Vn, nc, "d_n_lin2", batch.x, F)
+        node_sse, dVn = sigmoid_head(Vn, nc, "d_n_lin2", batch.x, F)
         # structure decoder (model.py:193-208) with its CE (optimizer.py:142-144)
         layers = [{"gamma": self.w(f"d_bn_e{i}/gamma"), "beta": self.w(f"d_bn_e{i}/beta"),
                    "w": self.w(f"e{i}_deconv/w1"), "b": self.w(f"e{i}_deconv/biases1")}
                   for i in range(len(cfg.e_d_hidden))]
         hd = {"gamma": self.w("decoder_adj/gamma"), "beta": self.w("decoder_adj/beta"),
               "w": self.w("d_e_lin2/Matrix"), "b": self.w("d_e_lin2/bias")}
-        adj_cost, correct, dz_e, eg, hg = structure_decoder(Jsg_g.view(B, N, 2 * nh), batch.adj_dense, layers, hd)
+        ce, dz_e, eg, hg = structure_decoder(Jsg_g.view(B, N, 2 * nh), batch.adj_dense, layers, hd,
+                                             device_out=True)
         for i, gi in enumerate(eg):
             self.g(f"d_bn_e{i}/gamma").copy_(gi["gamma"]); self.g(f"d_bn_e{i}/beta").copy_(gi["beta"])
             self.g(f"e{i}_deconv/w1").copy_(gi["w"]); self.g(f"e{i}_deconv/biases1").copy_(gi["b"])
@@ -412,14 +457,15 @@ class DisentangledSGCNModelVAE:
         self.g("d_e_lin2/Matrix").copy_(hg["w"]); self.g("d_e_lin2/bias").copy_(hg["b"])
         # spatial decoder (model.py:212-219): conv + BN x3 on [J_sg | J_s], sigmoid head
         slay, su, sc = conv_bn_chain(Jsg_s, "s", "d_bn_s", cfg.s_d_channel, 1)
-        spatial_cost, dsu = sigmoid_head(su, sc, "d_s_lin2", batch.spatial, cfg.spatial_dim)
-        # latent regularisers and the cost (optimizer.py:159-203)
-        cap = cfg.capacity
+        spatial_sse, dsu = sigmoid_head(su, sc, "d_s_lin2", batch.spatial, cfg.spatial_dim)
+        # latent regularisers (optimizer.py:159-190), per group in the order their terms are added
         groups = {"s": (ms_s[:, :cfg.s_latent].contiguous(), ms_s[:, cfg.s_latent:].contiguous(), z["s"]),
                   "g": (ms_g[:, :cfg.g_latent].contiguous(), ms_g[:, cfg.g_latent:].contiguous(), z["g"]),
                   "sg": (ms_sg[:, :cfg.sg_latent].contiguous(), ms_sg[:, cfg.sg_latent:].contiguous(), z["sg"])}
-        mse = {"adj_cost": adj_cost, "node_cost": node_cost, "spatial_cost": spatial_cost}
-        overall, reg_grads = disentangled_cost(cfg.model_type, groups, mse, cfg.beta, cfg.gamma, cap)
+        regs, reg_grads = {}, {}
+        for name, w in group_weights(cfg.model_type, cfg.beta, cfg.gamma, cap).items():
+            regs[name], dmu_r, ds_r = latent_reg(*groups[name], device_out=True, **w)
+            reg_grads[name] = (dmu_r, ds_r)
         # ================================ backward ================================
         def conv_bn_chain_bwd(lays, du, prefix, bnp, key):
             d = du
@@ -517,12 +563,7 @@ class DisentangledSGCNModelVAE:
                                            self.param_count, cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2,
                                            cfg.adam_eps, 1.0, _P(self.step_counter), _lib.stream_ptr()),
                    "snd_adam_tf1")
-        names = ("cost", "spatial_cost", "adj_cost", "node_cost") + \
-            (("kl_g", "kl_s", "kl_sg") if len(overall) == 7 else ("kl_sg",))   # overall_loss order
-        out = dict(zip(names, overall))
-        out["correct"] = correct
-        return out
-
+        return node_sse, spatial_sse, ce, regs
 
     # ---- inference: encode, decode, generate, traverse (model.py:153-358)
     def _n_graphs(self, batch: "DeviceDisentBatch") -> int:
@@ -658,6 +699,27 @@ class DisentangledSGCNModelVAE:
         for k in ("s", "g", "sg"):
             out[f"z_mean_{k}"] = enc[k]["mu"]
         return out
+
+    def evaluate(self, batch: "DeviceDisentBatch", mode: str = "mean", out=None):
+        """Edge-score counters (metrics.EdgeCounts) of the decoded batch against its adjacency:
+        generate(z=mode, want_margin=True), then snd_margin_eval bins the e2e decoder's margin
+        l1 - l0 against ``batch.adj_dense``.  The rule m > 0 is generated_adj's, so TP + FP is
+        its number of ones.  mode: 'mean' (the encoder means) or 'sample'.  ``out``: an
+        EdgeCounts over device tensors (EdgeCounts.zeros(B, device)) to add to and return, with
+        no host synchronisation; None returns fresh counters."""
+        from .layers import margin_eval
+        from .metrics import EdgeCounts
+        if mode not in ("mean", "sample"):
+            raise ValueError(f"evaluate: mode must be 'mean' or 'sample', got {mode!r}")
+        if out is not None and (not isinstance(out, EdgeCounts) or out.tensors is None):
+            raise ValueError("evaluate: out must be an EdgeCounts over device tensors")
+        gen = self.generate(batch, z=mode, want_margin=True)
+        hist, counts = out.tensors if out is not None else (None, None)
+        hist, counts = margin_eval(gen["margin"], batch.adj_dense, hist, counts, accumulate=out is not None)
+        if out is not None:
+            out.invalidate()
+            return out
+        return EdgeCounts(hist, counts)
 
     def _rows_to_device(self, rows):
         return [torch.from_numpy(np.ascontiguousarray(r, np.float32)).to(self.device) for r in rows]

@@ -293,9 +293,11 @@ def load_data_syn(type_: str, path: str, sampling_num: int = 10, num_feature: in
 
 
 def write_synthetic_dataset(path: str, cfg: SNDConfig, n_graphs: int, seed: int = 0,
-                            split: str = "train", adj_format: str = "npz") -> str:
+                            split: str = "train", adj_format: str = "npz", with_rel: bool = False) -> str:
     """Write seeded RGG graphs in the reference directory layout (scaled back
-    by 120 / 600 so ``load_data_syn`` recovers the generator's values)."""
+    by 120 / 600 so ``load_data_syn`` recovers the generator's values).  ``with_rel`` also
+    writes 2D_rel.npy [G, N, N], the pairwise distances of the written geometry, which the
+    spatial-graph encoder reads (``load_data_syn(load_rel=True)``)."""
     from .data import synthetic_batch
     b = synthetic_batch(cfg.replace(encoder_coords=False), n_graphs, seed=seed)
     n = cfg.n_nodes
@@ -312,7 +314,10 @@ def write_synthetic_dataset(path: str, cfg: SNDConfig, n_graphs: int, seed: int 
     else:
         raise ValueError(adj_format)
     np.save(os.path.join(d, "2D_node.npy"), b.feature_truth.reshape(n_graphs, n, -1) * NODE_SCALE)
-    np.save(os.path.join(d, "2D_geometry.npy"),
-            b.spatial_truth.reshape(n_graphs, n, -1) * COORD_SCALE)
+    geometry = b.spatial_truth.reshape(n_graphs, n, -1) * COORD_SCALE
+    np.save(os.path.join(d, "2D_geometry.npy"), geometry)
+    if with_rel:
+        np.save(os.path.join(d, "2D_rel.npy"),
+                np.sqrt(((geometry[:, :, None] - geometry[:, None]) ** 2).sum(-1)))
     np.save(os.path.join(d, "2D_prop.npy"), np.arange(n_graphs, dtype=np.float64)[:, None])
     return d

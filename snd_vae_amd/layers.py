@@ -246,6 +246,41 @@ def zzt_eval(z, rowptr, colidx, n_graphs, n, hist=None, counts=None, accumulate=
     return hist, counts
 
 
+def margin_eval(margin, adj, hist=None, counts=None, accumulate=False):
+    """``zzt_eval``'s counters for the e2e structure decoder (snd_margin_eval): the margin
+    l1 - l0 of ``disent.structure_decode(..., want_margin=True)`` binned and classified
+    against a dense adjacency.
+
+    margin, adj: contiguous float32 device tensors [B, N, N]; the label is adj != 0 and the
+    diagonal is skipped by index (counted as TN).  Returns (hist, counts): int64 [B, 2, 2048]
+    (label x margin bin of width 1/64 over [-16, 16)) and [B, 4] = {TP, FP, FN, TN} at
+    margin > 0, the format metrics.EdgeCounts takes.  Given ``hist`` / ``counts`` are cleared
+    first, or added to with ``accumulate``.  No host synchronisation."""
+    for t, name in ((margin, "margin"), (adj, "adj")):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 3
+                and t.shape[1] == t.shape[2] and t.shape[0] >= 1 and t.shape[1] >= 1):
+            raise ValueError(f"margin_eval {name}: expected a contiguous float32 device tensor [B, N, N]")
+    if margin.shape != adj.shape:
+        raise ValueError(f"margin_eval: margin {tuple(margin.shape)} and adj {tuple(adj.shape)} differ")
+    n_graphs, n = int(margin.shape[0]), int(margin.shape[1])
+    if (hist is None) != (counts is None):
+        raise ValueError("margin_eval: pass both hist and counts or neither")
+    if hist is None:
+        if accumulate:
+            raise ValueError("margin_eval: accumulate needs hist and counts")
+        hist = torch.empty(n_graphs, 2, 2048, dtype=torch.int64, device=margin.device)
+        counts = torch.empty(n_graphs, 4, dtype=torch.int64, device=margin.device)
+    for t, name, shape in ((hist, "hist", (n_graphs, 2, 2048)), (counts, "counts", (n_graphs, 4))):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int64 and tuple(t.shape) == shape):
+            raise ValueError(f"margin_eval {name}: expected a contiguous int64 device tensor {list(shape)}")
+    L = _lib.lib()
+    wsb = L.snd_margin_eval_workspace(n_graphs, n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=margin.device) if wsb else None
+    _lib.check(L.snd_margin_eval(_P(margin), _P(adj), n_graphs, n, _P(hist), _P(counts), int(bool(accumulate)),
+                                 _P(ws), wsb, _lib.stream_ptr()), "snd_margin_eval")
+    return hist, counts
+
+
 def zzt_edges(z, n_graphs, n, threshold=0.0, inclusive=False, capacity=None):
     """The predicted graph of the inner-product decoder as a CSR (snd_zzt_edges): L = z z^T
     per graph on the fp32 matrix cores, thresholded on chip; neither the logits nor a dense
