@@ -24,23 +24,18 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
+from .ops import f32
 
 _P = _lib.ptr
 
 MODEL_TYPES = ("base", "disentangled", "disentangled_C", "NED-VAE-IP", "beta-TCVAE", "geoGCN", "posGCN")
 
 
-def _f32(t, name):
-    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-        raise ValueError(f"{name}: expected a contiguous float32 device tensor")
-    return t
-
-
 def e2e(x, w1, b1):
     """e2e(input_, output_dim, k_h) of `layers.py:431-450`: x [B, N, N, C], w1 [K, C, O]
     (the [1, K, C, O] kernel), b1 [O] -> [B, N, N, O]."""
     for t, n in ((x, "x"), (w1, "w1"), (b1, "b1")):
-        _f32(t, f"e2e {n}")
+        f32(f"e2e {n}", t)
     B, N, N2, Cc = x.shape
     K, Cw, O = w1.shape
     if N2 != N or Cw != Cc or b1.numel() != O:
@@ -54,7 +49,7 @@ def e2e(x, w1, b1):
 def e2e_bwd(x, w1, dout):
     """(dx, dw1, db1) of sum(e2e(x, w1, b1) * dout)."""
     for t, n in ((x, "x"), (w1, "w1"), (dout, "dout")):
-        _f32(t, f"e2e_bwd {n}")
+        f32(f"e2e_bwd {n}", t)
     B, N, _, Cc = x.shape
     K, _, O = w1.shape
     dx = torch.empty_like(x)
@@ -72,10 +67,10 @@ def latent_reg(mu, logstd, z=None, w_kl=1.0, cap_gamma=0.0, cap_c=0.0, w_dip=0.0
     the path through z = mu + eps e^logstd (model.py:155-159).  ``device_out``: the first
     entry is snd_latent_reg's out[4] = {kl, term, dip, tc} left on the device (float64), with
     no host synchronisation."""
-    _f32(mu, "latent_reg mu")
-    _f32(logstd, "latent_reg logstd")
+    f32("latent_reg mu", mu)
+    f32("latent_reg logstd", logstd)
     if z is not None:
-        _f32(z, "latent_reg z")
+        f32("latent_reg z", z)
     if w_tc and z is None:
         raise ValueError("latent_reg: the total-correlation term needs the sample z")
     B, L = mu.shape
@@ -150,14 +145,14 @@ def structure_decode(z, layers, head, want_margin=False):
     [B, N, N] (1 iff logit 1 > logit 0, the diagonal 0), and with ``want_margin`` also the
     margin l1 - l0 as float32 [B, N, N] (-1 on the diagonal)."""
     B, N, D = z.shape
-    _f32(z, "structure_decode z")
+    f32("structure_decode z", z)
     if not layers:
         raise ValueError("structure_decode: at least one e2e layer")
     for i, lay in enumerate(layers):
         for k in ("gamma", "beta", "w", "b"):
-            _f32(lay[k], f"structure_decode layers[{i}][{k!r}]")
+            f32(f"structure_decode layers[{i}][{k!r}]", lay[k])
     for k in ("gamma", "beta", "w", "b"):
-        _f32(head[k], f"structure_decode head[{k!r}]")
+        f32(f"structure_decode head[{k!r}]", head[k])
     cin = 2 * D
     for i, lay in enumerate(layers):
         if tuple(lay["w"].shape[:2]) != (N, cin) or lay["gamma"].numel() != cin or lay["beta"].numel() != cin \
@@ -194,8 +189,8 @@ def structure_decoder(z, adj, layers, head, device_out=False):
     ``device_out``: instead of the first two entries, snd_e2e_head_ce's out[2] = {CE summed
     over B N^2, correct} left on the device (float64), with no host synchronisation."""
     B, N, D = z.shape
-    _f32(z, "structure_decoder z")
-    _f32(adj, "structure_decoder adj")
+    f32("structure_decoder z", z)
+    f32("structure_decoder adj", adj)
     L_ = _lib.lib()
     sp = _lib.stream_ptr()
     # forward: x0 = relu(BN0(pair(z))), y_{i+1} = e2e(x_i), x_i = relu(BN_i(y_i))

@@ -22,9 +22,10 @@ encoders, three latents, three decoders --
   latent regularisers (`disent.disentangled_cost`), overall_loss in the reference order.
 
 Every forward and backward operation is a HIP kernel of libsndvae.so reached through
-the C ABI (GEMM, CSR SpMM with the GraphConvolution epilogue, conv1d, frozen-BN +
-activation, SpatialGraphConvolution, reparameterisation, e2e, regularisers, sigmoid
-MSE heads, TF1 Adam); torch only allocates, views and copies device memory.  The
+the C ABI, the shared fp32 entry points by way of the host wrappers of ``ops.py`` (GEMM,
+CSR SpMM with the GraphConvolution epilogue, conv1d, frozen-BN + activation,
+SpatialGraphConvolution, reparameterisation, e2e, regularisers, sigmoid MSE heads, TF1
+Adam); torch only allocates, views and copies device memory.  The
 reference's scale is small (N = 25, B = 10, S = 10: `main.py:100,173-217`), so the
 model is a host-ordered composition of launches, not a fused plan.
 """
@@ -32,16 +33,17 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from dataclasses import dataclass
+from types import SimpleNamespace as NS
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .config import CONV_K
 from .data import SGBatch
 from .disent import group_weights, latent_reg, structure_decode, structure_decoder
-from .layers import conv1d_same_bwd, graph_convolution, spmm
+from .layers import graph_convolution, spmm
 from .params import _glorot_uniform, _truncated_normal
 from .sg import SGGraph, layer_param_shapes, make_layer
 
@@ -174,42 +176,18 @@ def init_blocks(cfg: DisentangledConfig, seed: int = 0) -> Dict[str, np.ndarray]
     return out
 
 
-# ------------------------------------------------------------------------------ op helpers
-def _gemm(a, b, c, m, n, k, ta=False, tb=False, lda=None, ldb=None, ldc=None, bias=None):
-    """c[m, n] = op(a) op(b) (+ bias) on MFMA (snd_gemm, fp32); views with explicit strides."""
-    lda = lda if lda is not None else (m if ta else k)
-    ldb = ldb if ldb is not None else (k if tb else n)
-    ldc = ldc if ldc is not None else n
-    _lib.check(_lib.lib().snd_gemm(int(ta), int(tb), m, n, k, _P(a), lda, _P(b), ldb, _P(c), ldc, _P(bias), 0,
-                                   _lib.stream_ptr()), "snd_gemm")
-
-
-def _bn_act(y, ldy, rows, c, g, b, act, act_first, x, ldx):
-    _lib.check(_lib.lib().snd_bn_act_fwd(_P(y), ldy, rows, c, _P(g), _P(b), act, int(act_first), _P(x), ldx,
-                                         _lib.stream_ptr()), "snd_bn_act_fwd")
-
-
-def _bn_act_bwd(dx, lddx, y, ldy, rows, c, g, b, act, act_first, dy, lddy, dg, db):
-    _lib.check(_lib.lib().snd_bn_act_bwd(_P(dx), lddx, _P(y), ldy, rows, c, _P(g), _P(b), act, int(act_first),
-                                         _P(dy), lddy, _P(dg), _P(db), _lib.stream_ptr()), "snd_bn_act_bwd")
-
-
-def _add(x, ldx, y, ldy, rows, cols, alpha=1.0):
-    _lib.check(_lib.lib().snd_add_strided(rows, cols, alpha, _P(x), ldx, _P(y), ldy, _lib.stream_ptr()),
-               "snd_add_strided")
-
-
-def _conv(x, ldx, rows, npg, cin, w, cout, bias, out):
-    _lib.check(_lib.lib().snd_conv1d_same_fwd(_P(x), ldx, rows, npg, cin, _P(w), cout, _P(bias), None, None,
-                                              None, cout, _P(out), cout, 0, _lib.stream_ptr()),
-               "snd_conv1d_same_fwd")
-
-
-RELU, LRELU, IDENT = 1, 2, 0
+RELU, LRELU, IDENT = ops.RELU, ops.LRELU, ops.IDENT
 
 # DisentangledSGCNModelVAE.losses (snd_disent_losses): optimizer.py:201's overall_loss, then
 # main.py:334's count of correct adjacency entries
 LOSS_NAMES = ("cost", "spatial_cost", "adj_cost", "node_cost", "kl_g", "kl_s", "kl_sg", "correct")
+
+
+def latent_groups(cfg: DisentangledConfig, n_graphs: int):
+    """(name, rows, latent) of the three latent groups, in the order a step walks them: one
+    row per graph for s and g, one per spanning-tree copy for sg."""
+    return (("s", n_graphs, cfg.s_latent), ("g", n_graphs, cfg.g_latent),
+            ("sg", n_graphs * cfg.sampling_num, cfg.sg_latent))
 
 
 class DisentangledSGCNModelVAE:
@@ -236,13 +214,13 @@ class DisentangledSGCNModelVAE:
         self.step_counter = torch.zeros(1, dtype=torch.int32, device=device)
         self.losses = torch.zeros(len(LOSS_NAMES), dtype=torch.float64, device=device)   # step_device()
         self.load_blocks(blocks if blocks is not None else init_blocks(cfg, seed))
-        S, B = cfg.sampling_num, n_graphs
-        avg = np.zeros((B, B * S), np.float32)                   # zbar = avg @ z_sg (model.py:180)
-        for b in range(B):
-            avg[b, b * S:(b + 1) * S] = 1.0 / S
-        self._avg = torch.from_numpy(avg).to(device)
-        self._ones = torch.ones(max(B * S * cfg.n_nodes, 1), device=device)
-        self._avg_cache = {}                                         # decode(): the mean over S' copies
+        self._avgs = {}                                               # (B, S') -> the mean over S' copies
+        self._avg = self._avg_matrix(n_graphs, cfg.sampling_num)
+        self._ones = torch.ones(max(n_graphs * cfg.sampling_num * cfg.n_nodes, 1), device=device)   # colsum
+        # (conv, BN) block names of the three conv1d + BN chains
+        self.chains = {"enc_s": [(f"g_s{i + 1}_conv", f"g_bn_s{i}") for i in range(len(cfg.s_channel))],
+                       "dec_n": [(f"n{i}_deconv", f"d_bn_n{i}") for i in range(len(cfg.n_d_channel))],
+                       "dec_s": [(f"s{i + 1}_deconv", f"d_bn_s{i}") for i in range(len(cfg.s_d_channel))]}
         f = cfg.num_feature
         self.sg_layers = []
         for i, hid in enumerate(cfg.sg_conv_hidden):
@@ -273,77 +251,115 @@ class DisentangledSGCNModelVAE:
         flat = self.grads.double().cpu().numpy()
         return {k: flat[self.offsets[k]:self.offsets[k] + int(np.prod(s))].reshape(s) for k, s in self.shapes.items()}
 
-    def _colsum(self, dy, rows, cols, out, ld=None):
-        """out[cols] = sum over rows of dy (a 1 x rows by rows x cols GEMM: bias gradients)."""
-        _gemm(self._ones, dy, out, 1, cols, rows, ta=True, lda=1, ldb=ld if ld is not None else cols)
+    # ---- pieces shared by the step and the inference
+    def _bn(self, name, y, act=IDENT):
+        """act(BN_name(y)) (frozen Keras BN)."""
+        return ops.bn_act(y, self.w(name + "/gamma"), self.w(name + "/beta"), act, False)
+
+    def _bn_bwd(self, name, dx, y, act=IDENT, act_first=False):
+        """dy of BN block ``name`` at its input y; its dgamma / dbeta go to the gradient buffer.
+        dx may be wider than y (its first columns are read)."""
+        return ops.bn_act_bwd(dx, y, self.w(name + "/gamma"), self.w(name + "/beta"), act, act_first,
+                              dgamma=self.g(name + "/gamma"), dbeta=self.g(name + "/beta"), lddx=dx.shape[1])[0]
+
+    def _colsum(self, dy, name):
+        """Bias gradient ``name`` = sum over the rows of dy."""
+        ops.colsum(dy, out=self.g(name), ones=self._ones)
+
+    def _chain(self, h, names, act, keep=False):
+        """conv1d(k=5, SAME) + BN + act per (conv, BN) block of ``names`` (model.py:119-129,
+        189-191, 214-216).  Returns the output and, with ``keep``, each layer's (input, conv
+        output) for ``_chain_bwd``."""
+        kept = []
+        for conv, bn in names:
+            y = ops.conv1d_same(h, self.w(conv + "/kernel"), self.w(conv + "/bias"), self.cfg.n_nodes)[0]
+            if keep:
+                kept.append((h, y))
+            h = self._bn(bn, y, act)
+        return h, kept
+
+    def _chain_bwd(self, d, kept, names, act):
+        """Backward of ``_chain``: the blocks' gradients into the gradient buffer; returns the
+        gradient at the chain's input."""
+        for (conv, bn), (h, y) in zip(reversed(names), reversed(kept)):
+            dy = self._bn_bwd(bn, d, y, act)
+            d = ops.conv1d_same_bwd_data(dy, self.w(conv + "/kernel"), self.cfg.n_nodes)
+            self.g(conv + "/kernel").copy_(ops.conv1d_same_bwd_weight(h, dy, self.cfg.n_nodes))
+            self._colsum(dy, conv + "/bias")
+        return d
+
+    def _avg_matrix(self, B, S):
+        """[B, B * S] with zbar = avg @ z_sg the mean over a graph's S copies (model.py:180)."""
+        avg = self._avgs.get((B, S))
+        if avg is None:
+            a = np.zeros((B, B * S), np.float32)
+            for b in range(B):
+                a[b, b * S:(b + 1) * S] = 1.0 / S
+            avg = self._avgs[(B, S)] = torch.from_numpy(a).to(self.device)
+        return avg
+
+    def _e2e_blocks(self, get):
+        """(layers, head) dicts of ``disent.structure_decoder`` over the parameters (get =
+        self.w) or their gradients (self.g)."""
+        layers = [{"gamma": get(f"d_bn_e{i}/gamma"), "beta": get(f"d_bn_e{i}/beta"),
+                   "w": get(f"e{i}_deconv/w1"), "b": get(f"e{i}_deconv/biases1")}
+                  for i in range(len(self.cfg.e_d_hidden))]
+        head = {"gamma": get("decoder_adj/gamma"), "beta": get("decoder_adj/beta"),
+                "w": get("d_e_lin2/Matrix"), "b": get("d_e_lin2/bias")}
+        return layers, head
+
+    def _decoder_front(self, z, avg):
+        """Latents {'s', 'g', 'sg'} to the decoders' inputs (model.py:172-184): J = d_*_lin1 of
+        z_s, z_g and the mean of z_sg over the copies (``avg``; None: one copy per graph).
+        Returns [J_sg | J_g], [J_sg | J_s] as [B * N, 2 node_h] and the projections' inputs
+        {'sg': the mean, 's', 'g'}, which the backward reads."""
+        N, nh = self.cfg.n_nodes, self.cfg.node_h
+        R = z["s"].shape[0] * N
+        zin = dict(z)
+        if avg is not None:                                           # the mean commutes with d_sg_lin1
+            zin["sg"] = ops.gemm(avg, z["sg"])
+        J = {k: ops.gemm(zin[k], self.w(f"d_{k}_lin1/Matrix"), bias=self.w(f"d_{k}_lin1/bias")).view(R, nh)
+             for k in ("sg", "s", "g")}
+        Jsg_g, Jsg_s = (torch.empty(R, 2 * nh, device=self.device) for _ in range(2))
+        Jsg_g[:, :nh].copy_(J["sg"]); Jsg_g[:, nh:].copy_(J["g"])
+        Jsg_s[:, :nh].copy_(J["sg"]); Jsg_s[:, nh:].copy_(J["s"])
+        return Jsg_g, Jsg_s, zin
 
     # ---- the three encoders (model.py:104-151), shared by step() and encode()
-    def _encoders(self, batch: "DeviceDisentBatch", B: int):
-        """Forward of the graph, spatial and spatial-graph encoders for a batch of B graphs:
-        (graph layers, spatial layers, SG output, heads, widths, (ms_g, ms_s, ms_sg)) with
-        ms = [mu | logstd] per row; everything step()'s backward reads."""
-        cfg = self.cfg
-        N, F, S = cfg.n_nodes, cfg.num_feature, cfg.sampling_num
-        R, RS = B * N, B * S * N
-        dev = self.device
-        T = lambda *shape: torch.empty(*shape, device=dev)
+    def _head(self, name, feat, rows):
+        """The flat heads <name>1_lin -> [<name>2_lin | <name>3_lin] over feat viewed as
+        [rows, K]: (feat, hidden, ms) with ms = [mu | logstd] per row."""
+        feat = feat.view(rows, -1)
+        hh = ops.gemm(feat, self.w(f"{name}1_lin/Matrix"), bias=self.w(f"{name}1_lin/bias"))
+        return feat, hh, ops.gemm(hh, self.w(f"{name}23_lin/Matrix"), bias=self.w(f"{name}23_lin/bias"))
+
+    def _encoders(self, batch: "DeviceDisentBatch", B: int) -> NS:
+        """Forward of the graph, spatial and spatial-graph encoders for a batch of B graphs,
+        with everything the backward reads: gl (graph layers: input, preactivation), H (their
+        output before BN encoder_g), sl / Us (the spatial chain's layers and output), sg_out,
+        heads {'s' | 'g' | 'sg': (feat, hidden, ms)}."""
+        cfg, e = self.cfg, NS(gl=[], heads={})
         # graph encoder (model.py:104-115)
-        x = batch.x
-        gl = []
-        hin, fin = x, F
-        for i, h in enumerate(cfg.g_conv_hidden):
-            last = i + 1 == len(cfg.g_conv_hidden)
+        hin, n_g = batch.x, len(cfg.g_conv_hidden)
+        for i in range(n_g):
+            last = i + 1 == n_g
             res = graph_convolution(batch.rowptr, batch.colidx, hin, self.w(f"g_g{i}_conv/w"),
-                                    self.w(f"g_bn_g{i}/gamma"), self.w(f"g_bn_g{i}/beta"), concat_x=x,
+                                    self.w(f"g_bn_g{i}/gamma"), self.w(f"g_bn_g{i}/beta"), concat_x=batch.x,
                                     enc_gamma=self.w("encoder_g/gamma") if last else None,
                                     enc_beta=self.w("encoder_g/beta") if last else None)
-            gl.append((hin, fin) + tuple(res))
-            hin, fin = res[0], h + F
-        G = gl[-1][4]                                                 # BN encoder_g output [R, W]
-        Wg = fin
-        heads = {}
-
-        def head(name, feat, rows, K, hidden, lat):
-            hh = T(rows, hidden)
-            _gemm(feat, self.w(f"{name}1_lin/Matrix"), hh, rows, hidden, K, bias=self.w(f"{name}1_lin/bias"))
-            ms = T(rows, 2 * lat)
-            _gemm(hh, self.w(f"{name}23_lin/Matrix"), ms, rows, 2 * lat, hidden, bias=self.w(f"{name}23_lin/bias"))
-            heads[name] = (feat, rows, K, hidden, lat, hh, ms)
-            return ms
-        ms_g = head("g_g", G, B, N * Wg, cfg.g_hidden, cfg.g_latent)
+            e.gl.append((hin, res[1]))
+            hin = res[0]
+        e.H = hin
+        e.heads["g"] = self._head("g_g", res[2], B)                   # res[2]: BN encoder_g
         # spatial encoder (model.py:119-129)
-        sl = []
-        hs, cin = batch.spatial, cfg.spatial_dim
-        for i, co in enumerate(cfg.s_channel):
-            y = T(R, co)
-            _conv(hs, cin, R, N, cin, self.w(f"g_s{i + 1}_conv/kernel"), co, self.w(f"g_s{i + 1}_conv/bias"), y)
-            u = T(R, co)
-            _bn_act(y, co, R, co, self.w(f"g_bn_s{i}/gamma"), self.w(f"g_bn_s{i}/beta"), RELU, False, u, co)
-            sl.append((hs, cin, y, u))
-            hs, cin = u, co
-        Vs = T(R, cin)
-        _bn_act(hs, cin, R, cin, self.w("encoder_s/gamma"), self.w("encoder_s/beta"), IDENT, False, Vs, cin)
-        Ws = cin
-        ms_s = head("g_s", Vs, B, N * Ws, cfg.s_hidden, cfg.s_latent)
+        e.Us, e.sl = self._chain(batch.spatial, self.chains["enc_s"], RELU, keep=True)
+        e.heads["s"] = self._head("g_s", self._bn("encoder_s", e.Us), B)
         # spatial-graph encoder (model.py:134-151) over the B*S copies
-        sg_in = batch.x_sg
+        e.sg_out = batch.x_sg
         for layer in self.sg_layers:
-            sg_in, _ = layer.forward(batch.sg_graph, sg_in)
-        Wsg = cfg.sg_conv_hidden[-1][-1]
-        sg_out = sg_in
-        Vsg = T(RS, Wsg)
-        _bn_act(sg_out, Wsg, RS, Wsg, self.w("encoder_sg/gamma"), self.w("encoder_sg/beta"), IDENT, False, Vsg, Wsg)
-        ms_sg = head("g_sg", Vsg, B * S, N * Wsg, cfg.sg_hidden, cfg.sg_latent)
-        return gl, sl, sg_out, heads, (Wg, Ws, Wsg), (ms_g, ms_s, ms_sg)
-
-    def _reparam(self, ms, rows, lat, eps):
-        """z = mu + eps e^logstd (model.py:153-161) over ms = [mu | logstd] rows."""
-        zz = torch.empty(rows, lat, device=self.device)
-        kl = torch.zeros(max(1, _lib.lib().snd_reparam_kl_blocks(rows, lat)), dtype=torch.float64,
-                         device=self.device)
-        _lib.check(_lib.lib().snd_reparam_kl(_P(ms), 2 * lat, rows, lat, _P(eps), 0, None, None, _P(zz),
-                                             _P(kl), _lib.stream_ptr()), "snd_reparam_kl")
-        return zz
+            e.sg_out, _ = layer.forward(batch.sg_graph, e.sg_out)
+        e.heads["sg"] = self._head("g_sg", self._bn("encoder_sg", e.sg_out), B * cfg.sampling_num)
+        return e
 
     # ---- one training step
     def step(self, batch: "DeviceDisentBatch", eps: Dict[str, torch.Tensor]) -> Dict[str, float]:
@@ -385,185 +401,118 @@ class DisentangledSGCNModelVAE:
             _P(self.losses), _lib.stream_ptr()), "snd_disent_losses")
 
     def _step(self, batch: "DeviceDisentBatch", eps: Dict[str, torch.Tensor], cap: float):
-        """The launches of one step, shared by step() and step_device().  Returns what the loss
-        terms are made of, on the device: (sse partials, count) of the node and of the spatial
-        head, snd_e2e_head_ce's {CE sum, correct} and snd_latent_reg's out[4] per group."""
-        cfg, B = self.cfg, self.B
-        N, F, nh, S = cfg.n_nodes, cfg.num_feature, cfg.node_h, cfg.sampling_num
-        R, RS = B * N, B * S * N
-        dev = self.device
-        T = lambda *shape: torch.empty(*shape, device=dev)
+        """The launches of one step, shared by step() and step_device(), stage by stage.
+        Returns what the loss terms are made of, on the device: (sse partials, count) of the
+        node and of the spatial head, snd_e2e_head_ce's {CE sum, correct} and snd_latent_reg's
+        out[4] per group."""
         self.grads.zero_()
-        # ================================ encoders ================================
-        gl, sl, sg_out, heads, (Wg, Ws, Wsg), (ms_g, ms_s, ms_sg) = self._encoders(batch, B)
-        # get_z (model.py:153-161)
-        z = {}
-        for name, ms, rows, lat in (("s", ms_s, B, cfg.s_latent), ("g", ms_g, B, cfg.g_latent),
-                                    ("sg", ms_sg, B * S, cfg.sg_latent)):
-            z[name] = self._reparam(ms, rows, lat, eps[name])
-        # ================================ decoder =================================
-        zbar = T(B, cfg.sg_latent)
-        _gemm(self._avg, z["sg"], zbar, B, cfg.sg_latent, B * S)
-        Jsg_g, Jsg_s = T(R, 2 * nh), T(R, 2 * nh)                     # [J_sg | J_g], [J_sg | J_s]
-        J = {}
-        for name, zz, lat in (("sg", zbar, cfg.sg_latent), ("s", z["s"], cfg.s_latent), ("g", z["g"], cfg.g_latent)):
-            j = T(B, N * nh)
-            _gemm(zz, self.w(f"d_{name}_lin1/Matrix"), j, B, N * nh, lat, bias=self.w(f"d_{name}_lin1/bias"))
-            J[name] = j.view(R, nh)
-        Jsg_g[:, :nh].copy_(J["sg"]); Jsg_g[:, nh:].copy_(J["g"])
-        Jsg_s[:, :nh].copy_(J["sg"]); Jsg_s[:, nh:].copy_(J["s"])
+        e = self._encode_z(batch, eps)
+        d = self._decode_losses(batch, e, cap)
+        self._backward_encoders(batch, eps, e, d, self._backward_decoders(d))
+        self._adam()
+        return d.node_sse, d.spatial_sse, d.ce, d.regs
 
-        def conv_bn_chain(inp, prefix, bnp, chans, key):
-            out, cin = [], 2 * nh
-            h = inp
-            for i, co in enumerate(chans):
-                y = T(R, co)
-                _conv(h, cin, R, N, cin, self.w(f"{prefix}{i + key}_deconv/kernel"), co,
-                      self.w(f"{prefix}{i + key}_deconv/bias"), y)
-                u = T(R, co)
-                _bn_act(y, co, R, co, self.w(f"{bnp}{i}/gamma"), self.w(f"{bnp}{i}/beta"), IDENT, False, u, co)
-                out.append((h, cin, y, u))
-                h, cin = u, co
-            return out, h, cin
+    def _encode_z(self, batch, eps) -> NS:
+        """Stage 1: the encoders and get_z (model.py:153-161), z = mu + eps e^logstd per group."""
+        e = self._encoders(batch, self.B)
+        e.z = {k: ops.reparam_kl(e.heads[k][2], eps[k])[0] for k, _, _ in latent_groups(self.cfg, self.B)}
+        return e
 
-        def sigmoid_head(u, cin, wname, target, cout):
-            ws_n = _lib.lib().snd_sigmoid_mse_blocks(R)
-            sse = torch.zeros(ws_n, dtype=torch.float64, device=dev)
-            yhat, du = T(R, cout), T(R, cin)
-            ws = torch.empty(ws_n * (cin * cout + cout), device=dev)
-            _lib.check(_lib.lib().snd_sigmoid_mse(_P(u), cin, R, cin, _P(self.w(wname + "/Matrix")),
-                                                  _P(self.w(wname + "/bias")), cout, _P(target), cout, _P(sse),
-                                                  _P(yhat), _P(du), cin, _P(self.g(wname + "/Matrix")),
-                                                  _P(self.g(wname + "/bias")), _P(ws), ws.numel() * 4,
-                                                  _lib.stream_ptr()), "snd_sigmoid_mse")
-            return (sse, R * cout), du
+    def _sigmoid_head(self, u, wname, target):
+        """sigmoid(linear) against target with its MSE: ((sse partials, count), du); the head's
+        gradients are added into the (zeroed) gradient buffer."""
+        sse, _, du, _, _ = ops.sigmoid_mse(u, self.w(wname + "/Matrix"), self.w(wname + "/bias"), target,
+                                           dw=self.g(wname + "/Matrix"), db=self.g(wname + "/bias"))
+        return (sse, target.numel()), du
+
+    def _decode_losses(self, batch, e: NS, cap: float) -> NS:
+        """Stage 2: the three decoders forward with their losses and the gradients the fused
+        loss kernels leave (the sigmoid heads', the structure decoder's, the regularisers')."""
+        cfg, B = self.cfg, self.B
+        Jsg_g, Jsg_s, zin = self._decoder_front(e.z, self._avg)
+        d = NS(zin=zin)
         # node decoder (model.py:186-191): conv + BN (no activation) x2, BN decoder_node, sigmoid head
-        nlay, nu, nc = conv_bn_chain(Jsg_g, "n", "d_bn_n", cfg.n_d_channel, 0)
-        Vn = T(R, nc)
-        _bn_act(nu, nc, R, nc, self.w("decoder_node/gamma"), self.w("decoder_node/beta"), IDENT, False, Vn, nc)
-        node_sse, dVn = sigmoid_head(Vn, nc, "d_n_lin2", batch.x, F)
+        d.nu, d.nlay = self._chain(Jsg_g, self.chains["dec_n"], IDENT, keep=True)
+        d.node_sse, d.dVn = self._sigmoid_head(self._bn("decoder_node", d.nu), "d_n_lin2", batch.x)
         # structure decoder (model.py:193-208) with its CE (optimizer.py:142-144)
-        layers = [{"gamma": self.w(f"d_bn_e{i}/gamma"), "beta": self.w(f"d_bn_e{i}/beta"),
-                   "w": self.w(f"e{i}_deconv/w1"), "b": self.w(f"e{i}_deconv/biases1")}
-                  for i in range(len(cfg.e_d_hidden))]
-        hd = {"gamma": self.w("decoder_adj/gamma"), "beta": self.w("decoder_adj/beta"),
-              "w": self.w("d_e_lin2/Matrix"), "b": self.w("d_e_lin2/bias")}
-        ce, dz_e, eg, hg = structure_decoder(Jsg_g.view(B, N, 2 * nh), batch.adj_dense, layers, hd,
-                                             device_out=True)
-        for i, gi in enumerate(eg):
-            self.g(f"d_bn_e{i}/gamma").copy_(gi["gamma"]); self.g(f"d_bn_e{i}/beta").copy_(gi["beta"])
-            self.g(f"e{i}_deconv/w1").copy_(gi["w"]); self.g(f"e{i}_deconv/biases1").copy_(gi["b"])
-        self.g("decoder_adj/gamma").copy_(hg["gamma"]); self.g("decoder_adj/beta").copy_(hg["beta"])
-        self.g("d_e_lin2/Matrix").copy_(hg["w"]); self.g("d_e_lin2/bias").copy_(hg["b"])
+        layers, head = self._e2e_blocks(self.w)
+        d.ce, d.dz_e, eg, hg = structure_decoder(Jsg_g.view(B, cfg.n_nodes, 2 * cfg.node_h), batch.adj_dense,
+                                                 layers, head, device_out=True)
+        glayers, ghead = self._e2e_blocks(self.g)
+        for dst, src in zip(glayers + [ghead], eg + [hg]):
+            for k in ("gamma", "beta", "w", "b"):
+                dst[k].copy_(src[k])
         # spatial decoder (model.py:212-219): conv + BN x3 on [J_sg | J_s], sigmoid head
-        slay, su, sc = conv_bn_chain(Jsg_s, "s", "d_bn_s", cfg.s_d_channel, 1)
-        spatial_sse, dsu = sigmoid_head(su, sc, "d_s_lin2", batch.spatial, cfg.spatial_dim)
+        su, d.slay = self._chain(Jsg_s, self.chains["dec_s"], IDENT, keep=True)
+        d.spatial_sse, d.dsu = self._sigmoid_head(su, "d_s_lin2", batch.spatial)
         # latent regularisers (optimizer.py:159-190), per group in the order their terms are added
-        groups = {"s": (ms_s[:, :cfg.s_latent].contiguous(), ms_s[:, cfg.s_latent:].contiguous(), z["s"]),
-                  "g": (ms_g[:, :cfg.g_latent].contiguous(), ms_g[:, cfg.g_latent:].contiguous(), z["g"]),
-                  "sg": (ms_sg[:, :cfg.sg_latent].contiguous(), ms_sg[:, cfg.sg_latent:].contiguous(), z["sg"])}
-        regs, reg_grads = {}, {}
+        groups = {k: (e.heads[k][2][:, :lat].contiguous(), e.heads[k][2][:, lat:].contiguous(), e.z[k])
+                  for k, _, lat in latent_groups(cfg, B)}
+        d.regs, d.reg_grads = {}, {}
         for name, w in group_weights(cfg.model_type, cfg.beta, cfg.gamma, cap).items():
-            regs[name], dmu_r, ds_r = latent_reg(*groups[name], device_out=True, **w)
-            reg_grads[name] = (dmu_r, ds_r)
-        # ================================ backward ================================
-        def conv_bn_chain_bwd(lays, du, prefix, bnp, key):
-            d = du
-            for i in range(len(lays) - 1, -1, -1):
-                h, cin, y, u = lays[i]
-                co = y.shape[1]
-                dy = T(R, co)
-                _bn_act_bwd(d, co, y, co, R, co, self.w(f"{bnp}{i}/gamma"), self.w(f"{bnp}{i}/beta"), IDENT, False,
-                            dy, co, self.g(f"{bnp}{i}/gamma"), self.g(f"{bnp}{i}/beta"))
-                dx, dw = conv1d_same_bwd(h, self.w(f"{prefix}{i + key}_deconv/kernel"), dy, N)
-                self.g(f"{prefix}{i + key}_deconv/kernel").copy_(dw)
-                self._colsum(dy, R, co, self.g(f"{prefix}{i + key}_deconv/bias"))
-                d = dx
-            return d
-        dn = T(R, nc)
-        _bn_act_bwd(dVn, nc, nu, nc, R, nc, self.w("decoder_node/gamma"), self.w("decoder_node/beta"), IDENT, False,
-                    dn, nc, self.g("decoder_node/gamma"), self.g("decoder_node/beta"))
-        dJsg_g = conv_bn_chain_bwd(nlay, dn, "n", "d_bn_n", 0)                   # [R, 2 nh]
-        _add(dz_e.view(R, 2 * nh), 2 * nh, dJsg_g, 2 * nh, R, 2 * nh)
-        dJsg_s = conv_bn_chain_bwd(slay, dsu, "s", "d_bn_s", 1)
-        dJ = {"sg": T(R, nh), "g": T(R, nh), "s": T(R, nh)}
+            d.regs[name], dmu_r, ds_r = latent_reg(*groups[name], device_out=True, **w)
+            d.reg_grads[name] = (dmu_r, ds_r)
+        return d
+
+    def _backward_decoders(self, d: NS) -> Dict[str, torch.Tensor]:
+        """Stage 3a: from the heads' gradients through the decoder chains, the concatenations
+        and the d_*_lin1 projections to dz per group (reconstruction path)."""
+        cfg, B = self.cfg, self.B
+        N, nh = cfg.n_nodes, cfg.node_h
+        R = B * N
+        dJsg_g = self._chain_bwd(self._bn_bwd("decoder_node", d.dVn, d.nu), d.nlay, self.chains["dec_n"], IDENT)
+        ops.add_strided(d.dz_e.view(R, 2 * nh), dJsg_g)
+        dJsg_s = self._chain_bwd(d.dsu, d.slay, self.chains["dec_s"], IDENT)
+        dJ = {k: torch.empty(R, nh, device=self.device) for k in ("sg", "g", "s")}
         dJ["sg"].copy_(dJsg_g[:, :nh]); dJ["g"].copy_(dJsg_g[:, nh:]); dJ["s"].copy_(dJsg_s[:, nh:])
-        _add(dJsg_s, 2 * nh, dJ["sg"], nh, R, nh)
+        ops.add_strided(dJsg_s[:, :nh], dJ["sg"], ldx=2 * nh)
         # projections (d_*_lin1) and the mean over the copies
         dz = {}
-        for name, zz, lat in (("sg", zbar, cfg.sg_latent), ("s", z["s"], cfg.s_latent), ("g", z["g"], cfg.g_latent)):
-            dflat = dJ[name].view(B, N * nh)
-            _gemm(zz, dflat, self.g(f"d_{name}_lin1/Matrix"), lat, N * nh, B, ta=True)
-            self._colsum(dflat, B, N * nh, self.g(f"d_{name}_lin1/bias"))
-            d = T(B, lat)
-            _gemm(dflat, self.w(f"d_{name}_lin1/Matrix"), d, B, lat, N * nh, tb=True)
-            dz[name] = d
-        dzsg = T(B * S, cfg.sg_latent)
-        _gemm(self._avg, dz["sg"], dzsg, B * S, cfg.sg_latent, B, ta=True)
-        dz["sg"] = dzsg
-        # reparameterisation (reconstruction path + the regulariser gradients) and the heads
+        for k in ("sg", "s", "g"):
+            dflat = dJ[k].view(B, N * nh)
+            ops.gemm(d.zin[k], dflat, ta=True, out=self.g(f"d_{k}_lin1/Matrix"))
+            self._colsum(dflat, f"d_{k}_lin1/bias")
+            dz[k] = ops.gemm(dflat, self.w(f"d_{k}_lin1/Matrix"), tb=True)
+        dz["sg"] = ops.gemm(self._avg, dz["sg"], ta=True)
+        return dz
+
+    def _backward_encoders(self, batch, eps, e: NS, d: NS, dz) -> None:
+        """Stage 3b: the reparameterisation (dz plus the regularisers' gradients), the flat
+        heads and the three encoders."""
         dfeat = {}
-        for name, key, lat in (("s", "g_s", cfg.s_latent), ("g", "g_g", cfg.g_latent), ("sg", "g_sg", cfg.sg_latent)):
-            feat, rows, K, hidden, _, hh, ms = heads[key]
-            dms = T(rows, 2 * lat)
-            dmu_r, ds_r = reg_grads.get(name, (None, None))
-            _lib.check(_lib.lib().snd_reparam_bwd(_P(ms), 2 * lat, rows, lat, _P(eps[name]), _P(dz[name]), _P(dmu_r),
-                                                  _P(ds_r), _P(dms), 2 * lat, _lib.stream_ptr()), "snd_reparam_bwd")
-            _gemm(hh, dms, self.g(f"{key}23_lin/Matrix"), hidden, 2 * lat, rows, ta=True)
-            self._colsum(dms, rows, 2 * lat, self.g(f"{key}23_lin/bias"))
-            dh = T(rows, hidden)
-            _gemm(dms, self.w(f"{key}23_lin/Matrix"), dh, rows, hidden, 2 * lat, tb=True)
-            _gemm(feat.view(rows, K), dh, self.g(f"{key}1_lin/Matrix"), K, hidden, rows, ta=True)
-            self._colsum(dh, rows, hidden, self.g(f"{key}1_lin/bias"))
-            df = T(rows, K)
-            _gemm(dh, self.w(f"{key}1_lin/Matrix"), df, rows, K, hidden, tb=True)
-            dfeat[name] = df
-        # spatial-graph encoder backward
-        dsg = T(RS, Wsg)
-        _bn_act_bwd(dfeat["sg"].view(RS, Wsg), Wsg, sg_out, Wsg, RS, Wsg, self.w("encoder_sg/gamma"),
-                    self.w("encoder_sg/beta"), IDENT, False, dsg, Wsg, self.g("encoder_sg/gamma"),
-                    self.g("encoder_sg/beta"))
-        d = dsg
+        for k, _, _ in latent_groups(self.cfg, self.B):
+            feat, hh, ms = e.heads[k]
+            dms = ops.reparam_bwd(ms, eps[k], dz[k], *d.reg_grads.get(k, (None, None)))
+            ops.gemm(hh, dms, ta=True, out=self.g(f"g_{k}23_lin/Matrix"))
+            self._colsum(dms, f"g_{k}23_lin/bias")
+            dh = ops.gemm(dms, self.w(f"g_{k}23_lin/Matrix"), tb=True)
+            ops.gemm(feat, dh, ta=True, out=self.g(f"g_{k}1_lin/Matrix"))
+            self._colsum(dh, f"g_{k}1_lin/bias")
+            dfeat[k] = ops.gemm(dh, self.w(f"g_{k}1_lin/Matrix"), tb=True)
+        # spatial-graph encoder
+        dsg = self._bn_bwd("encoder_sg", dfeat["sg"].view(e.sg_out.shape), e.sg_out)
         for i in range(len(self.sg_layers) - 1, -1, -1):
-            gr, d = self.sg_layers[i].backward(d, want_dx=i > 0)
+            gr, dsg = self.sg_layers[i].backward(dsg, want_dx=i > 0)
             self.g(f"g_sg{i}_conv").copy_(gr)
-        # spatial encoder backward
-        d = T(R, Ws)
-        _bn_act_bwd(dfeat["s"].view(R, Ws), Ws, sl[-1][3], Ws, R, Ws, self.w("encoder_s/gamma"),
-                    self.w("encoder_s/beta"), IDENT, False, d, Ws, self.g("encoder_s/gamma"), self.g("encoder_s/beta"))
-        for i in range(len(sl) - 1, -1, -1):
-            hs_i, cin, y, u = sl[i]
-            co = y.shape[1]
-            dy = T(R, co)
-            _bn_act_bwd(d, co, y, co, R, co, self.w(f"g_bn_s{i}/gamma"), self.w(f"g_bn_s{i}/beta"), RELU, False,
-                        dy, co, self.g(f"g_bn_s{i}/gamma"), self.g(f"g_bn_s{i}/beta"))
-            dx, dw = conv1d_same_bwd(hs_i, self.w(f"g_s{i + 1}_conv/kernel"), dy, N)
-            self.g(f"g_s{i + 1}_conv/kernel").copy_(dw)
-            self._colsum(dy, R, co, self.g(f"g_s{i + 1}_conv/bias"))
-            d = dx
-        # graph encoder backward (G = BN_enc(H2), H2 = [BN_1(lrelu(P1)) | x], ...)
-        dH = T(R, Wg)
-        Hn = gl[-1][2]
-        _bn_act_bwd(dfeat["g"].view(R, Wg), Wg, Hn, Wg, R, Wg, self.w("encoder_g/gamma"), self.w("encoder_g/beta"),
-                    IDENT, False, dH, Wg, self.g("encoder_g/gamma"), self.g("encoder_g/beta"))
-        for i in range(len(gl) - 1, -1, -1):
-            hin_i, fin_i, Pi = gl[i][0], gl[i][1], gl[i][3]
-            h = Pi.shape[1]
-            dP = T(R, h)
-            _bn_act_bwd(dH, dH.shape[1], Pi, h, R, h, self.w(f"g_bn_g{i}/gamma"), self.w(f"g_bn_g{i}/beta"), LRELU,
-                        True, dP, h, self.g(f"g_bn_g{i}/gamma"), self.g(f"g_bn_g{i}/beta"))
-            dXW = spmm(batch.rowptr, batch.colidx, dP)                          # A symmetric: A^T = A
-            _gemm(hin_i, dXW, self.g(f"g_g{i}_conv/w"), fin_i, h, R, ta=True)
+        # spatial encoder
+        self._chain_bwd(self._bn_bwd("encoder_s", dfeat["s"].view(e.Us.shape), e.Us), e.sl, self.chains["enc_s"], RELU)
+        # graph encoder (G = BN_enc(H2), H2 = [BN_1(lrelu(P1)) | x], ...)
+        dH = self._bn_bwd("encoder_g", dfeat["g"].view(e.H.shape), e.H)
+        for i in range(len(e.gl) - 1, -1, -1):
+            hin, P = e.gl[i]
+            dXW = spmm(batch.rowptr, batch.colidx, self._bn_bwd(f"g_bn_g{i}", dH, P, LRELU, True))   # A^T = A
+            ops.gemm(hin, dXW, ta=True, out=self.g(f"g_g{i}_conv/w"))
             if i > 0:
-                dH = T(R, fin_i)
-                _gemm(dXW, self.w(f"g_g{i}_conv/w"), dH, R, fin_i, h, tb=True)
-        # TF1 Adam (optimizer.py:125,197); the step counter is the TF global step
+                dH = ops.gemm(dXW, self.w(f"g_g{i}_conv/w"), tb=True)
+
+    def _adam(self) -> None:
+        """Stage 4: TF1 Adam (optimizer.py:125,197); the step counter is the TF global step."""
+        cfg = self.cfg
         self.step_counter += 1
         _lib.check(_lib.lib().snd_adam_tf1(_P(self.params), _P(self.grads), _P(self.m), _P(self.v),
                                            self.param_count, cfg.learning_rate, cfg.adam_beta1, cfg.adam_beta2,
                                            cfg.adam_eps, 1.0, _P(self.step_counter), _lib.stream_ptr()),
                    "snd_adam_tf1")
-        return node_sse, spatial_sse, ce, regs
 
     # ---- inference: encode, decode, generate, traverse (model.py:153-358)
     def _n_graphs(self, batch: "DeviceDisentBatch") -> int:
@@ -577,38 +526,18 @@ class DisentangledSGCNModelVAE:
         [, 'z']}}, rows [B, L] for s and g and per copy [B * S, Lsg] for sg (``mean_over_copies``
         averages them, main.py:407).  With eps = {'s': [B, Ls], 'g': [B, Lg], 'sg': [B*S, Lsg]}
         normals, z = mu + eps e^logstd (get_z, model.py:153-161) is included."""
-        cfg, B = self.cfg, self._n_graphs(batch)
-        ms_g, ms_s, ms_sg = self._encoders(batch, B)[5]
+        B = self._n_graphs(batch)
+        heads = self._encoders(batch, B).heads
         out = {}
-        for name, ms, rows, lat in (("s", ms_s, B, cfg.s_latent), ("g", ms_g, B, cfg.g_latent),
-                                    ("sg", ms_sg, B * cfg.sampling_num, cfg.sg_latent)):
+        for name, rows, lat in latent_groups(self.cfg, B):
+            ms = heads[name][2]
             out[name] = {"mu": ms[:, :lat].contiguous(), "logstd": ms[:, lat:].contiguous()}
             if eps is not None:
                 e = eps[name]
                 if tuple(e.shape) != (rows, lat) or e.dtype != torch.float32 or not e.is_contiguous():
                     raise ValueError(f"encode: eps[{name!r}] must be contiguous float32 [{rows}, {lat}]")
-                out[name]["z"] = self._reparam(ms, rows, lat, e)
+                out[name]["z"] = ops.reparam_kl(ms, e)[0]
         return out
-
-    def _chain(self, inp, R, prefix, bnp, chans, key):
-        """conv1d(k=5, SAME) + BN (no activation) per channel entry (model.py:189-191,214-216)."""
-        N = self.cfg.n_nodes
-        h, cin = inp, inp.shape[1]
-        for i, co in enumerate(chans):
-            y = torch.empty(R, co, device=self.device)
-            _conv(h, cin, R, N, cin, self.w(f"{prefix}{i + key}_deconv/kernel"), co,
-                  self.w(f"{prefix}{i + key}_deconv/bias"), y)
-            u = torch.empty(R, co, device=self.device)
-            _bn_act(y, co, R, co, self.w(f"{bnp}{i}/gamma"), self.w(f"{bnp}{i}/beta"), IDENT, False, u, co)
-            h, cin = u, co
-        return h, cin
-
-    def _sigmoid_linear(self, u, R, cin, wname, cout):
-        y = torch.empty(R, cout, device=self.device)
-        _lib.check(_lib.lib().snd_sigmoid_linear_fwd(_P(u), cin, R, cin, _P(self.w(wname + "/Matrix")),
-                                                     _P(self.w(wname + "/bias")), cout, _P(y), cout,
-                                                     _lib.stream_ptr()), "snd_sigmoid_linear_fwd")
-        return y
 
     def decode(self, z_s, z_sg, z_g, want_margin: bool = False) -> Dict[str, torch.Tensor]:
         """decoder(z_s, z_sg, z_g) of model.py:172-222 for any number of graphs B (not tied
@@ -617,7 +546,7 @@ class DisentangledSGCNModelVAE:
         Returns generated_adj uint8 [B, N, N] (the forward-only e2e decoder), generated_spatial
         [B, N, spatial_dim], generated_node_feat [B, N, F], and with want_margin the adjacency
         margin logit1 - logit0 [B, N, N]."""
-        cfg, dev = self.cfg, self.device
+        cfg = self.cfg
         N, F, nh = cfg.n_nodes, cfg.num_feature, cfg.node_h
         for t, lat, name in ((z_s, cfg.s_latent, "z_s"), (z_sg, cfg.sg_latent, "z_sg"), (z_g, cfg.g_latent, "z_g")):
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2
@@ -628,41 +557,16 @@ class DisentangledSGCNModelVAE:
         if z_g.shape[0] != B or rem or Sp < 1:
             raise ValueError(f"decode: z_s [{B}, Ls] needs z_g [{B}, Lg] and z_sg [{B} * S', Lsg], "
                              f"got {z_g.shape[0]} and {z_sg.shape[0]} rows")
-        R = B * N
-        T = lambda *shape: torch.empty(*shape, device=dev)
-        zbar = z_sg
-        if Sp > 1:                                                    # the mean commutes with d_sg_lin1
-            avg = self._avg_cache.get((B, Sp))
-            if avg is None:
-                a = np.zeros((B, B * Sp), np.float32)
-                for b in range(B):
-                    a[b, b * Sp:(b + 1) * Sp] = 1.0 / Sp
-                avg = self._avg_cache[(B, Sp)] = torch.from_numpy(a).to(dev)
-            zbar = T(B, cfg.sg_latent)
-            _gemm(avg, z_sg, zbar, B, cfg.sg_latent, B * Sp)
-        J = {}
-        for name, zz, lat in (("sg", zbar, cfg.sg_latent), ("s", z_s, cfg.s_latent), ("g", z_g, cfg.g_latent)):
-            j = T(B, N * nh)
-            _gemm(zz, self.w(f"d_{name}_lin1/Matrix"), j, B, N * nh, lat, bias=self.w(f"d_{name}_lin1/bias"))
-            J[name] = j.view(R, nh)
-        Jsg_g, Jsg_s = T(R, 2 * nh), T(R, 2 * nh)                     # [J_sg | J_g], [J_sg | J_s]
-        Jsg_g[:, :nh].copy_(J["sg"]); Jsg_g[:, nh:].copy_(J["g"])
-        Jsg_s[:, :nh].copy_(J["sg"]); Jsg_s[:, nh:].copy_(J["s"])
+        Jsg_g, Jsg_s, _ = self._decoder_front({"s": z_s, "g": z_g, "sg": z_sg},
+                                              self._avg_matrix(B, Sp) if Sp > 1 else None)
         # node features (model.py:186-194)
-        nu, nc = self._chain(Jsg_g, R, "n", "d_bn_n", cfg.n_d_channel, 0)
-        Vn = T(R, nc)
-        _bn_act(nu, nc, R, nc, self.w("decoder_node/gamma"), self.w("decoder_node/beta"), IDENT, False, Vn, nc)
-        node = self._sigmoid_linear(Vn, R, nc, "d_n_lin2", F)
+        nu, _ = self._chain(Jsg_g, self.chains["dec_n"], IDENT)
+        node = ops.sigmoid_linear(self._bn("decoder_node", nu), self.w("d_n_lin2/Matrix"), self.w("d_n_lin2/bias"))
         # adjacency (model.py:193-208)
-        layers = [{"gamma": self.w(f"d_bn_e{i}/gamma"), "beta": self.w(f"d_bn_e{i}/beta"),
-                   "w": self.w(f"e{i}_deconv/w1"), "b": self.w(f"e{i}_deconv/biases1")}
-                  for i in range(len(cfg.e_d_hidden))]
-        hd = {"gamma": self.w("decoder_adj/gamma"), "beta": self.w("decoder_adj/beta"),
-              "w": self.w("d_e_lin2/Matrix"), "b": self.w("d_e_lin2/bias")}
-        res = structure_decode(Jsg_g.view(B, N, 2 * nh), layers, hd, want_margin=want_margin)
+        res = structure_decode(Jsg_g.view(B, N, 2 * nh), *self._e2e_blocks(self.w), want_margin=want_margin)
         # coordinates (model.py:212-219)
-        su, sc = self._chain(Jsg_s, R, "s", "d_bn_s", cfg.s_d_channel, 1)
-        spatial = self._sigmoid_linear(su, R, sc, "d_s_lin2", cfg.spatial_dim)
+        su, _ = self._chain(Jsg_s, self.chains["dec_s"], IDENT)
+        spatial = ops.sigmoid_linear(su, self.w("d_s_lin2/Matrix"), self.w("d_s_lin2/bias"))
         out = {"generated_adj": res[0] if want_margin else res,
                "generated_spatial": spatial.view(B, N, cfg.spatial_dim),
                "generated_node_feat": node.view(B, N, F)}
@@ -684,12 +588,10 @@ class DisentangledSGCNModelVAE:
             gen = torch.Generator(device=self.device)
             gen.manual_seed(int(seed))
             eps = {k: torch.randn(rows, lat, device=self.device, generator=gen)
-                   for k, rows, lat in (("s", B, cfg.s_latent), ("g", B, cfg.g_latent),
-                                        ("sg", B * cfg.sampling_num, cfg.sg_latent))}
+                   for k, rows, lat in latent_groups(cfg, B)}
         enc = self.encode(batch, eps if z == "sample" else None)
         if z == "prior":
-            for k, rows, lat in (("s", B, cfg.s_latent), ("g", B, cfg.g_latent),
-                                 ("sg", B * cfg.sampling_num, cfg.sg_latent)):
+            for k, rows, lat in latent_groups(cfg, B):
                 if tuple(eps[k].shape) != (rows, lat):
                     raise ValueError(f"generate: eps[{k!r}] must be [{rows}, {lat}]")
             lat = {k: eps[k] for k in ("s", "g", "sg")}

@@ -28,7 +28,8 @@ from . import checkpoint as ckpt
 from . import layers
 from .config import sgjoint
 from .disent import capacity
-from .disent_model import LOSS_NAMES, DeviceDisentBatch, DisentangledConfig, DisentangledSGCNModelVAE
+from .disent_model import (LOSS_NAMES, DeviceDisentBatch, DisentangledConfig, DisentangledSGCNModelVAE,
+                           latent_groups)
 from .input_data import SynDataset, dataset_sg_batch
 
 # storer keys of main.py:335-345 -> LOSS_NAMES ('base' reports sg_kl only; adj_acc is derived)
@@ -38,8 +39,7 @@ STORER = (("loss", "cost"), ("spatial_loss", "spatial_cost"), ("adj_loss", "adj_
 
 def eps_shapes(cfg: DisentangledConfig, n_graphs: int) -> Dict[str, tuple]:
     """The normals one step reads: {'s': [B, Ls], 'g': [B, Lg], 'sg': [B*S, Lsg]}."""
-    return {"s": (n_graphs, cfg.s_latent), "g": (n_graphs, cfg.g_latent),
-            "sg": (n_graphs * cfg.sampling_num, cfg.sg_latent)}
+    return {k: (rows, lat) for k, rows, lat in latent_groups(cfg, n_graphs)}
 
 
 def _step_seed(seed: int, t: int) -> int:

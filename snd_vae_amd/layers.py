@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .model import DTYPES
 
 _P = _lib.ptr
@@ -27,11 +27,6 @@ def _dt(dtype):
     return DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
 
 
-def _need(t, name):
-    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-        raise ValueError(f"{name}: expected a contiguous float32 device tensor")
-
-
 def graph_convolution(rowptr, colidx, h, w, gamma=None, beta=None, concat_x=None,
                       enc_gamma=None, enc_beta=None, dtype="f32"):
     """GraphConvolution(adj, h, out) + BN + concat (model.py:107-112).
@@ -39,32 +34,19 @@ def graph_convolution(rowptr, colidx, h, w, gamma=None, beta=None, concat_x=None
     Returns (out, preact[, out2]).  Without gamma/beta: plain lrelu(A (h w))
     is not separable from BN in the fused kernel, so gamma=1, beta=0 is used.
     """
-    rows, fin = h.shape
     width = w.shape[1]
     xw = linear(h, w, None, dtype)
     if gamma is None:
         gamma = torch.ones(width, device=h.device)
         beta = torch.zeros(width, device=h.device)
-    fx = 0 if concat_x is None else concat_x.shape[1]
-    out = torch.empty(rows, width + fx, device=h.device)
-    pre = torch.empty(rows, width, device=h.device)
-    out2 = torch.empty_like(out) if enc_gamma is not None else None
-    _lib.check(_lib.lib().snd_csr_spmm(
-        _P(rowptr), _P(colidx), rows, _P(xw), width, width, _P(out), width + fx, 1,
-        _P(gamma), _P(beta), _P(pre), width, _P(concat_x), fx, fx, _P(enc_gamma),
-        _P(enc_beta), _P(out2), width + fx, _lib.stream_ptr()), "snd_csr_spmm")
+    out, pre, out2 = ops.spmm_gcn(rowptr, colidx, xw, gamma, beta, concat_x, enc_gamma, enc_beta)
     return (out, pre, out2) if out2 is not None else (out, pre)
 
 
 def spmm(rowptr, colidx, h):
     """A @ h on the block-diagonal CSR (tf.matmul(adj, x), layers.py:122)."""
-    _need(h, "spmm")
-    rows, width = h.shape
-    out = torch.empty_like(h)
-    _lib.check(_lib.lib().snd_csr_spmm(
-        _P(rowptr), _P(colidx), rows, _P(h), width, width, _P(out), width, 0, 0, 0, 0, 0,
-        0, 0, 0, 0, 0, 0, 0, _lib.stream_ptr()), "snd_csr_spmm")
-    return out
+    ops.f32("spmm", h)
+    return ops.spmm(rowptr, colidx, h)
 
 
 def spmm_bf16(rowptr, colidx, h, n_per_graph=0, n_graphs=0, row_order=None):
@@ -126,52 +108,30 @@ def spmm_bf16_window(wplan, h, n_per_graph, n_graphs):
 
 def linear(x, w, b=None, dtype="f32", trans_w=False):
     """x @ w + b (layers.py:566-576) on MFMA (fp32 or bf16 operands, fp32 acc)."""
-    _need(x, "linear x")
-    m, k = x.shape
-    n = w.shape[0] if trans_w else w.shape[1]
-    out = torch.empty(m, n, device=x.device)
-    _lib.check(_lib.lib().snd_gemm(0, int(trans_w), m, n, k, _P(x), k, _P(w), w.shape[1],
-                                   _P(out), n, _P(b), _dt(dtype), _lib.stream_ptr()), "snd_gemm")
-    return out
+    ops.f32("linear x", x)
+    return ops.gemm(x, w, tb=trans_w, bias=b, dtype=_dt(dtype))
 
 
 def conv1d_same(x, w, b, n_per_graph, gamma=None, beta=None, dtype="f32"):
     """conv1d(k=5, SAME) [+ BN + lrelu] over each graph's node axis.
 
     Returns out (and y_pre when BN is applied)."""
-    _need(x, "conv1d x")
-    rows, cin = x.shape
-    cout = w.shape[2]
-    out = torch.empty(rows, cout, device=x.device)
-    pre = torch.empty(rows, cout, device=x.device) if gamma is not None else None
-    _lib.check(_lib.lib().snd_conv1d_same_fwd(
-        _P(x), cin, rows, n_per_graph, cin, _P(w), cout, _P(b), _P(gamma), _P(beta), _P(pre),
-        cout, _P(out), cout, _dt(dtype), _lib.stream_ptr()), "snd_conv1d_same_fwd")
+    ops.f32("conv1d x", x)
+    out, pre = ops.conv1d_same(x, w, b, n_per_graph, gamma, beta, _dt(dtype))
     return (out, pre) if gamma is not None else out
 
 
 def conv1d_same_bwd(x, w, dy, n_per_graph, dtype="f32"):
     """(dx, dw) of conv1d SAME (TF autodiff of tf.layers.conv1d)."""
-    rows, cin = x.shape
-    cout = w.shape[2]
-    dx = torch.empty(rows, cin, device=x.device)
-    _lib.check(_lib.lib().snd_conv1d_same_bwd_data(
-        _P(dy), cout, rows, n_per_graph, cout, _P(w), cin, _P(dx), cin, _dt(dtype),
-        _lib.stream_ptr()), "snd_conv1d_same_bwd_data")
-    ws_n = _lib.lib().snd_conv1d_bwd_weight_workspace(rows, cin, cout)
-    ws = torch.empty(max(ws_n, 4), dtype=torch.uint8, device=x.device)
-    dw = torch.empty_like(w)
-    _lib.check(_lib.lib().snd_conv1d_same_bwd_weight(
-        _P(x), cin, _P(dy), cout, rows, n_per_graph, cin, cout, _P(dw), _P(ws), ws_n,
-        _dt(dtype), _lib.stream_ptr()), "snd_conv1d_same_bwd_weight")
-    return dx, dw
+    return (ops.conv1d_same_bwd_data(dy, w, n_per_graph, _dt(dtype)),
+            ops.conv1d_same_bwd_weight(x, dy, n_per_graph, _dt(dtype)))
 
 
 def inner_product_ce(z, n_graphs, rowptr, colidx, pos_weight=1.0, norm=1.0, dtype="bf16"):
     """InnerProductDecoder + diagonal rule + softmax CE, fused (no logits in HBM).
 
     Returns (ce_sum, n_correct, dz) with dz = d(ce_sum)/dz."""
-    _need(z, "inner_product_ce z")
+    ops.f32("inner_product_ce z", z)
     rows, d = z.shape
     n = rows // n_graphs
     L = _lib.lib()
@@ -194,7 +154,7 @@ def inner_product_ce_rows(z, row0, row1, rowptr, colidx, pos_weight=1.0, norm=1.
     Returns (stats, dz_rows): stats a float64 device tensor [ce_sum, n_correct] over the
     range (left on the device for the caller's all-reduce); dz_rows [row1 - row0, d] is
     d(ce_sum over ALL pairs)/dz for those rows (L symmetric: no reduction needed)."""
-    _need(z, "inner_product_ce_rows z")
+    ops.f32("inner_product_ce_rows z", z)
     n, d = z.shape
     L = _lib.lib()
     wsb = L.snd_zzt_ce_rows_workspace(n, d, row0, row1, _dt(dtype))

@@ -28,7 +28,8 @@ The arithmetic is a list of calls on an ``ops`` object (the HIP C ABI on the dev
 through a ``comm`` object (``TorchComm``: torch.distributed over RCCL, or gloo with the
 device tensors staged through host memory).  The fused single-device step
 (``snd_train_step``) stays the throughput path; this step is fp32 and composes ABI
-launches from the host, one per layer (``disent_model.py`` does the same).
+launches from the host, one per layer, through the wrappers of ``ops.py``
+(``disent_model.py`` does the same).
 """
 from __future__ import annotations
 
@@ -256,142 +257,68 @@ class TorchComm:
 
 # ---------------------------------------------------------------- HIP ops
 class HipOps:
-    """The step's arithmetic on the C ABI (fp32; every call one or two launches on the
-    current stream).  Elementwise glue (slices, concatenation, the KL gradient's two
-    vectors) stays in torch."""
+    """The step's arithmetic on the C ABI (``ops``: fp32, every call one or two launches on
+    the current stream).  What is specific to row sharding stays here: contiguous copies of
+    the step's slices, the rescale of the sigmoid heads to the whole graph's count, the KL
+    gradient's two vectors and the row-range CE."""
 
     def __init__(self):
-        from . import _lib
-        self._lib = _lib
+        from . import _lib, ops
+        self._lib, self.ops = _lib, ops
         self.L = _lib.lib()
         self.P = _lib.ptr
 
-    def _s(self):
-        return self._lib.stream_ptr()
-
-    def _gemm(self, ta, tb, m, n, k, a, lda, b, ldb, c, ldc, bias=None):
-        self._lib.check(self.L.snd_gemm(int(ta), int(tb), m, n, k, self.P(a), lda, self.P(b), ldb, self.P(c), ldc,
-                                        self.P(bias), 0, self._s()), "snd_gemm")
-
     def mm(self, a, b, bias=None):
-        m, k = a.shape
-        n = b.shape[1]
-        out = torch.empty(m, n, device=a.device)
-        self._gemm(0, 0, m, n, k, a.contiguous(), k, b.contiguous(), n, out, n, bias)
-        return out
+        return self.ops.gemm(a.contiguous(), b.contiguous(), bias=bias)
 
     def linear(self, x, w, b):
         return self.mm(x, w, b)
 
     def mm_tn(self, a, b):          # a^T b
-        m, k = a.shape
-        n = b.shape[1]
-        out = torch.empty(k, n, device=a.device)
-        self._gemm(1, 0, k, n, m, a.contiguous(), k, b.contiguous(), n, out, n)
-        return out
+        return self.ops.gemm(a.contiguous(), b.contiguous(), ta=True)
 
     def mm_nt(self, a, b):          # a b^T
-        m, n = a.shape
-        k = b.shape[0]
-        out = torch.empty(m, k, device=a.device)
-        self._gemm(0, 1, m, k, n, a.contiguous(), n, b.contiguous(), n, out, k)
-        return out
+        return self.ops.gemm(a.contiguous(), b.contiguous(), tb=True)
 
     def colsum(self, a):
-        m, n = a.shape
-        ones = torch.ones(m, 1, device=a.device)
-        out = torch.empty(1, n, device=a.device)
-        self._gemm(1, 0, 1, n, m, ones, 1, a.contiguous(), n, out, n)
-        return out.view(n)
+        return self.ops.colsum(a.contiguous())
 
     def spmm(self, csr: RowCSR, h):
-        width = h.shape[1]
-        out = torch.empty(csr.n_out, width, device=h.device)
-        self._lib.check(self.L.snd_csr_spmm(
-            self.P(csr.rowptr), self.P(csr.colidx), csr.n_out, self.P(h.contiguous()), width, width, self.P(out),
-            width, 0, None, None, None, 0, None, 0, 0, None, None, None, 0, self._s()), "snd_csr_spmm")
-        return out
+        return self.ops.spmm(csr.rowptr, csr.colidx, h.contiguous(), n_out=csr.n_out)
 
     def bn_act(self, y, gamma, beta, act, act_first):
-        rows, c = y.shape
-        x = torch.empty_like(y)
-        self._lib.check(self.L.snd_bn_act_fwd(self.P(y), c, rows, c, self.P(gamma), self.P(beta), act,
-                                              int(act_first), self.P(x), c, self._s()), "snd_bn_act_fwd")
-        return x
+        return self.ops.bn_act(y, gamma, beta, act, act_first)
 
     def bn_act_bwd(self, dx, y, gamma, beta, act, act_first):
-        rows, c = y.shape
-        dy = torch.empty_like(y)
-        dg = torch.empty(c, device=y.device)
-        db = torch.empty(c, device=y.device)
-        self._lib.check(self.L.snd_bn_act_bwd(self.P(dx.contiguous()), c, self.P(y), c, rows, c, self.P(gamma),
-                                              self.P(beta), act, int(act_first), self.P(dy), c, self.P(dg),
-                                              self.P(db), self._s()), "snd_bn_act_bwd")
-        return dy, dg, db
+        return self.ops.bn_act_bwd(dx.contiguous(), y, gamma, beta, act, act_first)
 
     def conv_bn_lrelu(self, x, w, b, gamma, beta):
-        rows, cin = x.shape
-        cout = w.shape[2]
-        y = torch.empty(rows, cout, device=x.device)
-        u = torch.empty(rows, cout, device=x.device)
-        self._lib.check(self.L.snd_conv1d_same_fwd(self.P(x), cin, rows, rows, cin, self.P(w), cout, self.P(b),
-                                                   self.P(gamma), self.P(beta), self.P(y), cout, self.P(u), cout, 0,
-                                                   self._s()), "snd_conv1d_same_fwd")
+        u, y = self.ops.conv1d_same(x, w, b, x.shape[0], gamma, beta)     # one graph: n_per_graph = rows
         return y, u
 
     def conv_bwd(self, x, w, dy):
-        rows, cin = x.shape
-        cout = w.shape[2]
-        dx = torch.empty(rows, cin, device=x.device)
-        self._lib.check(self.L.snd_conv1d_same_bwd_data(self.P(dy), cout, rows, rows, cout, self.P(w), cin,
-                                                        self.P(dx), cin, 0, self._s()), "snd_conv1d_same_bwd_data")
-        nws = self.L.snd_conv1d_bwd_weight_workspace(rows, cin, cout)
-        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
-        dw = torch.empty_like(w)
-        self._lib.check(self.L.snd_conv1d_same_bwd_weight(self.P(x), cin, self.P(dy), cout, rows, rows, cin, cout,
-                                                          self.P(dw), self.P(ws), nws, 0, self._s()),
-                        "snd_conv1d_same_bwd_weight")
-        return dx, dw
+        rows = x.shape[0]
+        return self.ops.conv1d_same_bwd_data(dy, w, rows), self.ops.conv1d_same_bwd_weight(x, dy, rows)
 
     def sigmoid_mse(self, u, w, b, target, count):
         """(sse over the rows, du, dw, db) with the mean over `count` elements (the whole
         graph's): the kernel's own denominator is rows * cout, rescaled here."""
-        rows, cin = u.shape
-        cout = w.shape[1]
-        nb = self.L.snd_sigmoid_mse_blocks(rows)
-        sse = torch.zeros(nb, dtype=torch.float64, device=u.device)
-        yhat = torch.empty(rows, cout, device=u.device)
-        du = torch.empty(rows, cin, device=u.device)
-        dw = torch.zeros_like(w)
-        db = torch.zeros_like(b)
-        ws = torch.empty(max(1, nb * (cin * cout + cout)), device=u.device)
-        self._lib.check(self.L.snd_sigmoid_mse(self.P(u), cin, rows, cin, self.P(w), self.P(b), cout,
-                                               self.P(target.contiguous()), cout, self.P(sse), self.P(yhat),
-                                               self.P(du), cin, self.P(dw), self.P(db), self.P(ws),
-                                               ws.numel() * 4, self._s()), "snd_sigmoid_mse")
-        sc = (rows * cout) / float(count)
+        sse, _, du, dw, db = self.ops.sigmoid_mse(u, w, b, target.contiguous())
+        sc = (u.shape[0] * w.shape[1]) / float(count)
         return float(sse.sum().item()), du * sc, dw * sc, db * sc
 
     def reparam(self, mu, s, eps):
         """z = mu + eps e^s and sum(1 + 2s - mu^2 - e^{2s}) over the rows (snd_reparam_kl)."""
-        rows, lat = mu.shape
-        ms = _cat(mu, s)
-        z = torch.empty(rows, lat, device=mu.device)
-        kl = torch.zeros(self.L.snd_reparam_kl_blocks(rows, lat), dtype=torch.float64, device=mu.device)
-        self._lib.check(self.L.snd_reparam_kl(self.P(ms), 2 * lat, rows, lat, self.P(eps.contiguous()), 0, None,
-                                              None, self.P(z), self.P(kl), self._s()), "snd_reparam_kl")
+        z, kl = self.ops.reparam_kl(_cat(mu, s), eps.contiguous())
         return z, float(kl.sum().item())
 
     def reparam_bwd(self, mu, s, eps, dz, kl_coef):
         """(dmu, ds) of z = mu + eps e^s plus kl_coef * d/d(mu, s) of -0.5 sum(1 + 2s - mu^2 - e^{2s})."""
-        rows, lat = mu.shape
+        lat = mu.shape[1]
         ms = _cat(mu, s)
         add_mu = (kl_coef * mu).contiguous()
         add_s = (kl_coef * torch.expm1(2.0 * s)).contiguous()
-        dms = torch.empty(rows, 2 * lat, device=mu.device)
-        self._lib.check(self.L.snd_reparam_bwd(self.P(ms), 2 * lat, rows, lat, self.P(eps.contiguous()),
-                                               self.P(dz), self.P(add_mu), self.P(add_s), self.P(dms), 2 * lat,
-                                               self._s()), "snd_reparam_bwd")
+        dms = self.ops.reparam_bwd(ms, eps.contiguous(), dz, add_mu, add_s)
         return dms[:, :lat], dms[:, lat:]
 
     def adj_ce_rows(self, z_full, plan: RowShardPlan, pos_weight, norm):
@@ -404,7 +331,7 @@ class HipOps:
         self._lib.check(self.L.snd_zzt_ce_rows(self.P(z_full.contiguous()), n, d, plan.r0, plan.r1,
                                                self.P(plan.ce_rowptr), self.P(plan.ce_colidx), float(pos_weight),
                                                float(norm), self.P(stats), self.P(dz), self.P(ws), wsb, 0,
-                                               self._s()), "snd_zzt_ce_rows")
+                                               self._lib.stream_ptr()), "snd_zzt_ce_rows")
         st = stats.cpu()
         return float(st[0]), float(st[1]), dz
 

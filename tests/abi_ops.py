@@ -1,8 +1,9 @@
 """Guarded, strided operands and float64 references for the stand-alone C ABI ops
 (include/snd_vae.h), plain NumPy: importable without a GPU.
 
-Outside callers (autograd.py, rowshard.py, disent_model.py, any FFI binding) hand the entry
-points raw pointers and leading dimensions.  This module gives every op
+Outside callers (ops.py, through which layers.py, autograd.py, rowshard.py and disent_model.py
+call, and any FFI binding) hand the entry points raw pointers and leading dimensions.  This
+module gives every op
 
 * its operands in *guarded* buffers: G guard elements, ``rows`` rows of ``ld`` elements,
   G guard elements, with the guards and the padding columns ``width..ld-1`` holding one
