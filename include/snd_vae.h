@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 23
+#define SND_ABI_VERSION 24
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -510,7 +510,9 @@ int snd_add_strided(long long rows, int cols, float alpha, const float* x, int l
  * TC the minibatch estimate of optimizer.py:29-58 (logvar = 2 logstd).  Writes
  * dmu / dlogstd = d term / d (mu, logstd) including the path through
  * z = mu + eps e^{logstd} (model.py:155-159), and out[4] (double) =
- * {kl, term, DIP, TC}.  One workgroup: sized for the reference's batches (<= a few
+ * {kl, term, DIP, TC}.  The TC block runs in double on the fp32 operands (its gradient
+ * weight is the difference of two softmaxes that nearly cancel at a small batch).
+ * One workgroup: sized for the reference's batches (<= a few
  * hundred latents).  workspace >= snd_latent_reg_workspace(batch, latent) bytes
  * when w_dip or w_tc is nonzero. */
 typedef struct {
@@ -558,6 +560,61 @@ int snd_e2e_decode(const float* z, int ldz, int n_graphs, int n, int d,
                    const float* head_w, const float* head_b,
                    unsigned char* adj, float* margin,
                    void* workspace, size_t workspace_bytes, snd_stream_t stream);
+
+/* ---- factorised training engine of the e2e structure decoder (ABI 24) ----------
+ * Forward, CE and every gradient of model.py:193-208 in one call, from z [n_graphs, n, d]
+ * (row stride ldz) and the dense 0/1 float target adj [n_graphs, n, n] (as
+ * snd_e2e_head_ce), without the pair tensor x0 [B, N, N, 2d] or its gradient.  Operands
+ * as for snd_e2e_decode; layer_grads[l] holds the destinations of layer l's gradients.
+ * Gradients of the MEAN CE (as snd_e2e_head_ce); every output is written, not
+ * accumulated.  dz [n_graphs, n, d] (row stride lddz).  out[2] (device double) =
+ * {CE summed over B N^2, correct}.
+ * Forward: snd_e2e_decode's route; every layer's y_l stays in the workspace and the
+ * backward recomputes relu(BN(.)) from it as operands are loaded.  The head, the CE and
+ * dy_last are snd_e2e_head_ce's kernel.
+ * Backward of a general layer (C -> O), g = dy_l, pb = (n-1)/2, x = relu(BN_l(y_{l-1})):
+ *   dw[t,c,o] = sum_{b,i,j} (x[b,i,j+t-pb,c] + x[b,i+t-pb,j,c]) g[b,i,j,o]   (out of range: 0)
+ *   db[o]     = 2 sum g
+ *   dx[b,i,j,c] = sum_t sum_o w[t,c,o] (g[b,i,j-t+pb,o] + g[b,i-t+pb,j,o])
+ *   dy_{l-1} = dx 1[BN_l(y_{l-1}) > 0] gamma_l BN_C;  dgamma_l, dbeta_l the per-channel sums
+ * The weight gradient is reduced per (tap, group of graphs) into slabs that a second
+ * kernel sums in index order.
+ * Backward of layer 0 through the factorisation, g = dy_0 [B, N, N, O]:
+ *   a = relu(BN0[:D](z)), a' = relu(BN0[D:](z)),
+ *   Wsum_n[c,o] = sum_{t: 0 <= n+t-pb < N} w[t,c,o],  R[b,i,o] = sum_j g,  S[b,j,o] = sum_i g
+ *   da[b,i,c]  = sum_j sum_o g[b,i,j,o] Wsum_j[c,o]   + sum_t sum_o R[b,i-t+pb,o] w[t,c,o]
+ *   da'[b,j,c] = sum_i sum_o g[b,i,j,o] Wsum_i[D+c,o] + sum_t sum_o S[b,j-t+pb,o] w[t,D+c,o]
+ *   dWsum_n[c,o]   = sum_{b,i} a[b,i,c] g[b,i,n,o];   dWsum_n[D+c,o] = sum_{b,j} a'[b,j,c] g[b,n,j,o]
+ *   dw[t,c,o]   = sum_{n: 0 <= n+t-pb < N} dWsum_n[c,o]   + sum_{b,i} a[b,i+t-pb,c] R[b,i,o]
+ *   dw[t,D+c,o] = sum_{n: 0 <= n+t-pb < N} dWsum_n[D+c,o] + sum_{b,j} a'[b,j+t-pb,c] S[b,j,o]
+ *   db[o] = 2 sum g
+ *   dz[b,n,c] = BN_C (gamma0[c] 1[a > 0] da[b,n,c] + gamma0[D+c] 1[a' > 0] da'[b,n,c])
+ *   dgamma0, dbeta0: the matching per-channel sums over (b, n).
+ * fp32 FMA, fixed summation order, no atomics (two runs are bitwise equal); no host
+ * synchronisation and no allocation (capturable in a graph).
+ * workspace >= snd_e2e_train_workspace bytes (0 for a bad shape): every layer's y, two
+ * gradient activations [B, n, n, max cout], the forward's weight image and per-node terms,
+ * R, S, dWsum, da | da', and the weight-gradient slabs (at most 32 of [n, cin, cout]).
+ * SND_ERR_ARG before anything touches the device: a null operand (every gradient is
+ * required), n_layers < 1 or > 16, a width < 1, n or a cout > 512, c_last > 32, ldz < d,
+ * lddz < d, a short workspace, n_graphs < 1 or > 262140; and, d being unbounded otherwise, a d
+ * whose layer-0 launches would not fit a grid (d > 2^24, or n 2 d cout_0 or n_graphs n 2 d
+ * over 2^31 x 256 threads). */
+typedef struct {
+  float *dgamma, *dbeta;   /* [cin] */
+  float *dw, *db;          /* [n, cin, cout], [cout] */
+} snd_e2e_layer_grad_t;
+size_t snd_e2e_train_workspace(int n_graphs, int n, int d, const int* couts, int n_layers);
+int snd_e2e_train(const float* z, int ldz, const float* adj, int n_graphs, int n, int d,
+                  const snd_e2e_layer_t* layers, int n_layers,
+                  const float* head_gamma, const float* head_beta,
+                  const float* head_w, const float* head_b,
+                  float* dz, int lddz,
+                  const snd_e2e_layer_grad_t* layer_grads,
+                  float* d_head_gamma, float* d_head_beta, float* d_head_w, float* d_head_b,
+                  double* out,
+                  void* workspace, size_t workspace_bytes, snd_stream_t stream);
+
 /* yhat = sigmoid(u w + b): the forward half of snd_sigmoid_mse for the decoders'
  * sigmoid heads at inference (no target).  u [rows, cin] (stride ldu), w [cin, cout],
  * yhat [rows, cout] (stride ldy). */

@@ -17,7 +17,7 @@ c_int, c_ll, c_float, c_size, c_ull = C.c_int, C.c_longlong, C.c_float, C.c_size
 vp = C.c_void_p
 
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 GEN_MODES = {"sample": 0, "mean": 1, "prior": 2, "given": 3}
 TOPOLOGY = {"tscale": 0, "tref": 1, "sgjoint": 2}
 
@@ -70,6 +70,11 @@ class LatentReg(C.Structure):
 class E2ELayer(C.Structure):
     """snd_e2e_layer_t (include/snd_vae.h)."""
     _fields_ = [("gamma", vp), ("beta", vp), ("w", vp), ("b", vp), ("cout", c_int)]
+
+
+class E2ELayerGrad(C.Structure):
+    """snd_e2e_layer_grad_t (include/snd_vae.h)."""
+    _fields_ = [("dgamma", vp), ("dbeta", vp), ("dw", vp), ("db", vp)]
 
 
 # name -> (restype, argtypes)
@@ -142,6 +147,9 @@ _SIGS = {
     "snd_e2e_decode_workspace": (c_size, [c_int, c_int, c_int, C.POINTER(c_int), c_int]),
     "snd_e2e_decode": (c_int, [vp, c_int, c_int, c_int, c_int, C.POINTER(E2ELayer), c_int, vp, vp, vp, vp, vp, vp,
                                vp, c_size, vp]),
+    "snd_e2e_train_workspace": (c_size, [c_int, c_int, c_int, C.POINTER(c_int), c_int]),
+    "snd_e2e_train": (c_int, [vp, c_int, vp, c_int, c_int, c_int, C.POINTER(E2ELayer), c_int, vp, vp, vp, vp, vp,
+                              c_int, C.POINTER(E2ELayerGrad), vp, vp, vp, vp, vp, vp, c_size, vp]),
     "snd_sigmoid_linear_fwd": (c_int, [vp, c_int, c_ll, c_int, vp, vp, c_int, vp, c_int, vp]),
     "snd_disent_losses": (c_int, [vp, c_int, C.c_double, vp, c_int, C.c_double, vp, C.c_double, vp, vp, vp, vp, vp]),
     "snd_margin_eval_workspace": (c_size, [c_int, c_int]),

@@ -19,7 +19,9 @@
 // kl = -0.5 mean(1 + 2 s - mu^2 - e^{2s}); DIP on the batch covariance of mu; TC the
 // minibatch estimate E_j[log q(z_j) - sum_l log q(z_jl)] with logvar = 2 s.  The
 // gradients with respect to mu and s include the path through z = mu + eps e^s
-// (model.py:155-159): d mu += dz, d s += dz (z - mu).
+// (model.py:155-159): d mu += dz, d s += dz (z - mu).  The TC block sums and exponentiates in
+// double on the fp32 operands: its gradient weight is the difference of two softmaxes that
+// nearly cancel at a small batch.
 #include "snd_common.hpp"
 
 #include <algorithm>
@@ -141,7 +143,7 @@ struct RegArgs {
   float* dmu;
   float* ds;
   double* out;   // [kl, term, dip, tc]
-  float* ws;     // DIP: L*L G + L mean | TC: B*B S, B*B*L lqp, B*L dz, B*L LSE_i lqp, B LSE_i S
+  float* ws;     // DIP: L*L G + L mean | TC: B*B S - row max, B*B*L lqp, B*L dz, B*L LSE_i lqp, B LSE_i (S - max)
 };
 
 __global__ void __launch_bounds__(RT) latent_reg_kernel(RegArgs a) {
@@ -202,75 +204,87 @@ __global__ void __launch_bounds__(RT) latent_reg_kernel(RegArgs a) {
   // ---- total correlation (optimizer.py:23-58), logvar = 2 s
   double tcv = 0.0;
   if (a.w_tc != 0.f) {
-    const float kLog2Pi = 1.8378770664093453f;
-    float* S = a.ws;                          // [j][i] sum_l lqp
+    // Every sum, softmax and difference below runs in double on the fp32 operands: at a small
+    // batch the two softmaxes nearly cancel and an fp32 running sum over L or a row sum S stored
+    // at its full magnitude (~ -L) costs the gradient 1e-4.  S is stored relative to its row max.
+    const double kLog2Pi = 1.8378770664093453;
+    float* S = a.ws;                          // [j][i] sum_l lqp - max_i of the row
     float* Q = a.ws + (long long)B * B;       // [j][i][l] lqp
     float* dz = Q + (long long)B * B * L;     // [j][l]
+    float* PL = dz + (long long)B * L;        // [j][l] LSE_i Q
+    float* SL = PL + (long long)B * L;        // [j]    the row max of S, then LSE_i (S - max)
     for (long long e = tid; e < (long long)B * B * L; e += RT) {
       const int l = (int)(e % L);
       const long long ji = e / L;
       const int i = (int)(ji % B), j = (int)(ji / B);
-      const float tmp = a.z[(long long)j * L + l] - a.mu[(long long)i * L + l];
-      const float sv = a.s[(long long)i * L + l];
-      Q[e] = -0.5f * (tmp * tmp * expf(-2.f * sv) + 2.f * sv + kLog2Pi);
+      const double tmp = (double)a.z[(long long)j * L + l] - (double)a.mu[(long long)i * L + l];
+      const double sv = a.s[(long long)i * L + l];
+      Q[e] = (float)(-0.5 * (tmp * tmp * exp(-2.0 * sv) + 2.0 * sv + kLog2Pi));
     }
     __syncthreads();
-    for (int e = tid; e < B * B; e += RT) {
-      float t = 0.f;
-      for (int l = 0; l < L; ++l) t += Q[(long long)e * L + l];
-      S[e] = t;
-    }
+    auto row_sum = [&](int e) {
+      double t = 0.0;
+      for (int l = 0; l < L; ++l) t += (double)Q[(long long)e * L + l];
+      return t;
+    };
+    for (int e = tid; e < B * B; e += RT) S[e] = (float)row_sum(e);
     __syncthreads();
-    // per j: log_qz = LSE_i S[j,i]; per (j, l): P = LSE_i Q[j,i,l]; W = (softmax_i S - softmax_i Q) / B
-    float* PL = dz + (long long)B * L;        // [j][l] LSE_i Q
-    float* SL = PL + (long long)B * L;        // [j]    LSE_i S
     for (int j = tid; j < B; j += RT) {
       float ms = -INFINITY;
       for (int i = 0; i < B; ++i) ms = fmaxf(ms, S[(long long)j * B + i]);
-      float ss = 0.f;
-      for (int i = 0; i < B; ++i) ss += expf(S[(long long)j * B + i] - ms);
-      SL[j] = ms + logf(ss);
+      SL[j] = ms;
+    }
+    __syncthreads();
+    for (int e = tid; e < B * B; e += RT) S[e] = (float)(row_sum(e) - (double)SL[e / B]);
+    __syncthreads();
+    // per j: log_qz = max + LSE_i S[j,i]; per (j, l): P = LSE_i Q[j,i,l]; W = (softmax_i S - softmax_i Q) / B
+    double tp = 0.0;
+    for (int j = tid; j < B; j += RT) {
+      double ss = 0.0;
+      for (int i = 0; i < B; ++i) ss += exp((double)S[(long long)j * B + i]);
+      const double ls = log(ss);
+      tp += (double)SL[j] + ls;
+      SL[j] = (float)ls;
     }
     for (int e = tid; e < B * L; e += RT) {
       const int j = e / L, l = e - j * L;
       float mx = -INFINITY;
       for (int i = 0; i < B; ++i) mx = fmaxf(mx, Q[((long long)j * B + i) * L + l]);
-      float sq = 0.f;
-      for (int i = 0; i < B; ++i) sq += expf(Q[((long long)j * B + i) * L + l] - mx);
-      PL[e] = mx + logf(sq);
+      double sq = 0.0;
+      for (int i = 0; i < B; ++i) sq += exp((double)Q[((long long)j * B + i) * L + l] - (double)mx);
+      const float pl = (float)((double)mx + log(sq));
+      PL[e] = pl;
+      tp -= (double)pl;
     }
     __syncthreads();
-    double tp = 0.0;
-    for (int j = tid; j < B; j += RT) tp += (double)SL[j];
-    for (int e = tid; e < B * L; e += RT) tp -= (double)PL[e];
     tcv = block_sum_d(tp, sh) / (double)B;
     auto wgt = [&](int j, int i, int l) {
-      return (expf(S[(long long)j * B + i] - SL[j]) - expf(Q[((long long)j * B + i) * L + l] - PL[(long long)j * L + l])) /
-             (float)B;
+      return (exp((double)S[(long long)j * B + i] - (double)SL[j]) -
+              exp((double)Q[((long long)j * B + i) * L + l] - (double)PL[(long long)j * L + l])) / (double)B;
     };
     for (int e = tid; e < B * L; e += RT) {   // (j, l): dz through the densities of sample j
       const int j = e / L, l = e - j * L;
-      const float zj = a.z[e];
-      float dzv = 0.f;
+      const double zj = a.z[e];
+      double dzv = 0.0;
       for (int i = 0; i < B; ++i)
-        dzv -= wgt(j, i, l) * (zj - a.mu[(long long)i * L + l]) * expf(-2.f * a.s[(long long)i * L + l]);
-      dz[e] = dzv;
+        dzv -= wgt(j, i, l) * (zj - (double)a.mu[(long long)i * L + l]) * exp(-2.0 * (double)a.s[(long long)i * L + l]);
+      dz[e] = (float)dzv;
     }
     __syncthreads();
     for (int e = tid; e < B * L; e += RT) {   // (i, l): d mu, d s through the densities
       const int i = e / L, l = e - i * L;
-      const float mi = a.mu[e], sv = a.s[e], iv = expf(-2.f * sv);
-      float dm = 0.f, dsv = 0.f;
+      const double mi = a.mu[e], iv = exp(-2.0 * (double)a.s[e]);
+      double dm = 0.0, dsv = 0.0;
       for (int j = 0; j < B; ++j) {
-        const float w = wgt(j, i, l);
-        const float tmp = a.z[(long long)j * L + l] - mi;
+        const double w = wgt(j, i, l);
+        const double tmp = (double)a.z[(long long)j * L + l] - mi;
         dm += w * tmp * iv;
-        dsv += w * (tmp * tmp * iv - 1.f);
+        dsv += w * (tmp * tmp * iv - 1.0);
       }
       // through z_i = mu_i + eps_i e^{s_i}: d mu += dz, d s += dz (z - mu)
-      const float dzi = dz[e];
-      a.dmu[e] += a.w_tc * (dm + dzi);
-      a.ds[e] += a.w_tc * (dsv + dzi * (a.z[e] - mi));
+      const double dzi = dz[e];
+      a.dmu[e] += a.w_tc * (float)(dm + dzi);
+      a.ds[e] += a.w_tc * (float)(dsv + dzi * ((double)a.z[e] - mi));
     }
   }
   if (tid == 0) {

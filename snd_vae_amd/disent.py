@@ -145,23 +145,7 @@ def structure_decode(z, layers, head, want_margin=False):
     [B, N, N] (1 iff logit 1 > logit 0, the diagonal 0), and with ``want_margin`` also the
     margin l1 - l0 as float32 [B, N, N] (-1 on the diagonal)."""
     B, N, D = z.shape
-    f32("structure_decode z", z)
-    if not layers:
-        raise ValueError("structure_decode: at least one e2e layer")
-    for i, lay in enumerate(layers):
-        for k in ("gamma", "beta", "w", "b"):
-            f32(f"structure_decode layers[{i}][{k!r}]", lay[k])
-    for k in ("gamma", "beta", "w", "b"):
-        f32(f"structure_decode head[{k!r}]", head[k])
-    cin = 2 * D
-    for i, lay in enumerate(layers):
-        if tuple(lay["w"].shape[:2]) != (N, cin) or lay["gamma"].numel() != cin or lay["beta"].numel() != cin \
-                or lay["b"].numel() != lay["w"].shape[2]:
-            raise ValueError(f"structure_decode: layer {i} wants gamma/beta [{cin}], w [{N}, {cin}, O], b [O]")
-        cin = lay["w"].shape[2]
-    if tuple(head["w"].shape) != (cin, 2) or head["gamma"].numel() != cin or head["beta"].numel() != cin \
-            or head["b"].numel() != 2:
-        raise ValueError(f"structure_decode: head wants gamma/beta [{cin}], w [{cin}, 2], b [2]")
+    _check_decoder_operands("structure_decode", z, layers, head)
     L_ = _lib.lib()
     n = len(layers)
     couts = (C.c_int * n)(*[int(lay["w"].shape[2]) for lay in layers])
@@ -177,7 +161,62 @@ def structure_decode(z, layers, head, want_margin=False):
     return (adj, margin) if want_margin else adj
 
 
-def structure_decoder(z, adj, layers, head, device_out=False):
+ENGINES = ("direct", "factorised")
+
+
+def _check_decoder_operands(what, z, layers, head):
+    """The validation of ``structure_decode``, shared with ``structure_decoder``'s factorised engine."""
+    B, N, D = z.shape
+    f32(f"{what} z", z)
+    if not layers:
+        raise ValueError(f"{what}: at least one e2e layer")
+    for i, lay in enumerate(layers):
+        for k in ("gamma", "beta", "w", "b"):
+            f32(f"{what} layers[{i}][{k!r}]", lay[k])
+    for k in ("gamma", "beta", "w", "b"):
+        f32(f"{what} head[{k!r}]", head[k])
+    cin = 2 * D
+    for i, lay in enumerate(layers):
+        if tuple(lay["w"].shape[:2]) != (N, cin) or lay["gamma"].numel() != cin or lay["beta"].numel() != cin \
+                or lay["b"].numel() != lay["w"].shape[2]:
+            raise ValueError(f"{what}: layer {i} wants gamma/beta [{cin}], w [{N}, {cin}, O], b [O]")
+        cin = lay["w"].shape[2]
+    if tuple(head["w"].shape) != (cin, 2) or head["gamma"].numel() != cin or head["beta"].numel() != cin \
+            or head["b"].numel() != 2:
+        raise ValueError(f"{what}: head wants gamma/beta [{cin}], w [{cin}, 2], b [2]")
+
+
+def _structure_decoder_factorised(z, adj, layers, head, device_out, grads_out):
+    from .ops import e2e_train
+    B, N, D = z.shape
+    _check_decoder_operands("structure_decoder", z, layers, head)
+    if tuple(adj.shape) != (B, N, N):
+        raise ValueError(f"structure_decoder: adj wants [{B}, {N}, {N}]")
+    if grads_out is None:
+        grads = [{k: torch.empty_like(lay[k]) for k in ("gamma", "beta", "w", "b")} for lay in layers]
+        hg = {k: torch.empty_like(head[k]) for k in ("gamma", "beta", "w", "b")}
+    else:
+        grads, hg = grads_out
+        if len(grads) != len(layers):
+            raise ValueError("structure_decoder: grads_out wants one dict per layer")
+        for i, (g, lay) in enumerate(zip(grads, layers)):
+            for k in ("gamma", "beta", "w", "b"):
+                f32(f"structure_decoder grads_out[0][{i}][{k!r}]", g[k])
+                if g[k].numel() != lay[k].numel():
+                    raise ValueError(f"structure_decoder: grads_out[0][{i}][{k!r}] has the wrong size")
+        for k in ("gamma", "beta", "w", "b"):
+            f32(f"structure_decoder grads_out[1][{k!r}]", hg[k])
+            if hg[k].numel() != head[k].numel():
+                raise ValueError(f"structure_decoder: grads_out[1][{k!r}] has the wrong size")
+    dz = torch.empty_like(z)
+    out = e2e_train(z, adj, layers, head, dz, grads, hg)
+    if device_out:
+        return out, dz, grads, hg
+    o = out.cpu().tolist()
+    return o[0] / (B * N * N), o[1], dz, grads, hg
+
+
+def structure_decoder(z, adj, layers, head, device_out=False, engine="direct", grads_out=None):
     """The e2e structure decoder of `model.py:193-208` with the CE of `optimizer.py:142-144`,
     forward and backward in one call.
 
@@ -187,10 +226,20 @@ def structure_decoder(z, adj, layers, head, device_out=False):
     (adj_cost = mean CE over B N^2, correct = #(argmax == A) (main.py:334), dz,
     grads: a list of per-layer dicts and the head dict, same keys as the inputs).
     ``device_out``: instead of the first two entries, snd_e2e_head_ce's out[2] = {CE summed
-    over B N^2, correct} left on the device (float64), with no host synchronisation."""
+    over B N^2, correct} left on the device (float64), with no host synchronisation.
+
+    ``engine``: "direct" (the default) forms the pair tensor and runs one op per stage;
+    "factorised" is one call of ``snd_e2e_train``, which never forms the pair tensor or its
+    gradient (operands validated as in ``structure_decode``).  ``grads_out``: an optional
+    (layer dicts, head dict) of destination tensors the gradients are written into and
+    which are returned; without it fresh tensors are returned."""
+    if engine not in ENGINES:
+        raise ValueError(f"structure_decoder: unknown engine {engine!r} (one of {ENGINES})")
     B, N, D = z.shape
     f32("structure_decoder z", z)
     f32("structure_decoder adj", adj)
+    if engine == "factorised":
+        return _structure_decoder_factorised(z, adj, layers, head, device_out, grads_out)
     L_ = _lib.lib()
     sp = _lib.stream_ptr()
     # forward: x0 = relu(BN0(pair(z))), y_{i+1} = e2e(x_i), x_i = relu(BN_i(y_i))
@@ -233,6 +282,11 @@ def structure_decoder(z, adj, layers, head, device_out=False):
             _lib.check(L_.snd_e2e_pair_bwd(_P(dx), _P(z), B, N, D, _P(l0["gamma"]), _P(l0["beta"]), _P(dz),
                                            _P(grads[0]["gamma"]), _P(grads[0]["beta"]), _P(ws), sp),
                        "snd_e2e_pair_bwd")
+    if grads_out is not None:
+        for src, dst in zip(grads + [hg], list(grads_out[0]) + [grads_out[1]]):
+            for k in ("gamma", "beta", "w", "b"):
+                dst[k].copy_(src[k].view_as(dst[k]))
+        grads, hg = grads_out
     if device_out:
         return out, dz, grads, hg
     o = out.cpu().tolist()

@@ -42,7 +42,7 @@ import torch
 from . import _lib, ops
 from .config import CONV_K
 from .data import SGBatch
-from .disent import group_weights, latent_reg, structure_decode, structure_decoder
+from .disent import ENGINES, group_weights, latent_reg, structure_decode, structure_decoder
 from .layers import graph_convolution, spmm
 from .params import _glorot_uniform, _truncated_normal
 from .sg import SGGraph, layer_param_shapes, make_layer
@@ -197,10 +197,13 @@ class DisentangledSGCNModelVAE:
     means, prior samples) and the latent traversals ``traverse`` / ``traverse_all``."""
 
     def __init__(self, cfg: DisentangledConfig, n_graphs: int, blocks: Optional[Dict[str, np.ndarray]] = None,
-                 seed: int = 0, device="cuda"):
+                 seed: int = 0, device="cuda", e2e_engine: str = "direct"):
         if not torch.cuda.is_available():
             raise _lib.SNDError("the disentangled model needs a ROCm GPU (no CPU fallback)")
+        if e2e_engine not in ENGINES:
+            raise ValueError(f"unknown e2e_engine {e2e_engine!r} (one of {ENGINES})")
         self.cfg, self.B, self.device = cfg, n_graphs, device
+        self.e2e_engine = e2e_engine      # the training structure decoder; not part of the config (checkpoints)
         self.shapes = block_shapes(cfg)
         self.offsets, off = {}, 0
         for k, shp in self.shapes.items():
@@ -436,12 +439,17 @@ class DisentangledSGCNModelVAE:
         d.node_sse, d.dVn = self._sigmoid_head(self._bn("decoder_node", d.nu), "d_n_lin2", batch.x)
         # structure decoder (model.py:193-208) with its CE (optimizer.py:142-144)
         layers, head = self._e2e_blocks(self.w)
-        d.ce, d.dz_e, eg, hg = structure_decoder(Jsg_g.view(B, cfg.n_nodes, 2 * cfg.node_h), batch.adj_dense,
-                                                 layers, head, device_out=True)
         glayers, ghead = self._e2e_blocks(self.g)
-        for dst, src in zip(glayers + [ghead], eg + [hg]):
-            for k in ("gamma", "beta", "w", "b"):
-                dst[k].copy_(src[k])
+        if self.e2e_engine == "factorised":     # one call, written straight into the gradient buffer
+            d.ce, d.dz_e, _, _ = structure_decoder(Jsg_g.view(B, cfg.n_nodes, 2 * cfg.node_h), batch.adj_dense,
+                                                   layers, head, device_out=True, engine="factorised",
+                                                   grads_out=(glayers, ghead))
+        else:
+            d.ce, d.dz_e, eg, hg = structure_decoder(Jsg_g.view(B, cfg.n_nodes, 2 * cfg.node_h), batch.adj_dense,
+                                                     layers, head, device_out=True)
+            for dst, src in zip(glayers + [ghead], eg + [hg]):
+                for k in ("gamma", "beta", "w", "b"):
+                    dst[k].copy_(src[k])
         # spatial decoder (model.py:212-219): conv + BN x3 on [J_sg | J_s], sigmoid head
         su, d.slay = self._chain(Jsg_s, self.chains["dec_s"], IDENT, keep=True)
         d.spatial_sse, d.dsu = self._sigmoid_head(su, "d_s_lin2", batch.spatial)

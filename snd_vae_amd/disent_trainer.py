@@ -66,8 +66,10 @@ def draw_step_eps(seed: int, t: int, out: Dict[str, torch.Tensor]) -> Dict[str, 
 class DisentTrainer:
     def __init__(self, cfg: DisentangledConfig, dataset: SynDataset, batch_size: int, seed: int = 1234,
                  use_graphs: bool = False, blocks=None, device="cuda", c_max: Optional[float] = None,
-                 c_step: int = 20, c_stop_iter: int = 100):
-        """c_max / c_step / c_stop_iter: the capacity schedule of 'disentangled_C'
+                 c_step: int = 20, c_stop_iter: int = 100, e2e_engine: str = "direct"):
+        """e2e_engine: the model's training structure decoder ("direct" or "factorised"; not
+        part of the config, so checkpoints restore under either).
+        c_max / c_step / c_stop_iter: the capacity schedule of 'disentangled_C'
         (`optimizer.py:167`, global_iter = the epoch, `main.py:329`); c_max None keeps
         cfg.capacity for every epoch."""
         self.cfg, self.batch_size, self.seed = cfg, batch_size, seed
@@ -80,7 +82,8 @@ class DisentTrainer:
             DeviceDisentBatch(dataset_sg_batch(dataset, data_cfg, range(i * batch_size, (i + 1) * batch_size)),
                               device=device)
             for i in range(self.batch_num)]
-        self.model = DisentangledSGCNModelVAE(cfg, batch_size, blocks=blocks, seed=seed, device=device)
+        self.model = DisentangledSGCNModelVAE(cfg, batch_size, blocks=blocks, seed=seed, device=device,
+                                              e2e_engine=e2e_engine)
         self.eps = {k: torch.empty(*shp, device=device) for k, shp in eps_shapes(cfg, batch_size).items()}
         self.use_graphs = use_graphs
         self.c_max, self.c_step, self.c_stop_iter = c_max, c_step, c_stop_iter

@@ -193,3 +193,27 @@ def add_strided(x, y, alpha=1.0, ldx=None, ldy=None):
     _lib.check(_lib.lib().snd_add_strided(rows, cols, alpha, _P(x), cols if ldx is None else ldx, _P(y),
                                           cols if ldy is None else ldy, _lib.stream_ptr()), "snd_add_strided")
     return y
+
+
+def e2e_train(z, adj, layers, head, dz, layer_grads, head_grads):
+    """Forward, CE and every gradient of the e2e structure decoder in one call (snd_e2e_train,
+    the factorised engine).  z [B, N, D], adj [B, N, N] float 0/1; layers / head: dicts of
+    gamma, beta, w, b; dz, layer_grads, head_grads: destinations of the same shapes, written
+    (not accumulated).  Returns out float64 [2] = {CE summed over B N^2, correct}, on the device."""
+    import ctypes as C
+    B, N, D = z.shape
+    n = len(layers)
+    L_ = _lib.lib()
+    couts = (C.c_int * n)(*[int(lay["w"].shape[2]) for lay in layers])
+    arr = (_lib.E2ELayer * n)(*[_lib.E2ELayer(_P(lay["gamma"]), _P(lay["beta"]), _P(lay["w"]), _P(lay["b"]),
+                                              int(lay["w"].shape[2])) for lay in layers])
+    garr = (_lib.E2ELayerGrad * n)(*[_lib.E2ELayerGrad(_P(g["gamma"]), _P(g["beta"]), _P(g["w"]), _P(g["b"]))
+                                     for g in layer_grads])
+    nbytes = int(L_.snd_e2e_train_workspace(B, N, D, couts, n))
+    ws = torch.empty(max(nbytes, 16), device=z.device, dtype=torch.uint8)
+    out = torch.empty(2, device=z.device, dtype=torch.float64)
+    _lib.check(L_.snd_e2e_train(_P(z), D, _P(adj), B, N, D, arr, n, _P(head["gamma"]), _P(head["beta"]),
+                                _P(head["w"]), _P(head["b"]), _P(dz), D, garr, _P(head_grads["gamma"]),
+                                _P(head_grads["beta"]), _P(head_grads["w"]), _P(head_grads["b"]), _P(out), _P(ws),
+                                ws.numel(), _lib.stream_ptr()), "snd_e2e_train")
+    return out

@@ -16,9 +16,12 @@ is taken around each block, which ends in a device synchronise, and divided by t
 For ``replay`` HIP events around every replay give the device-side time as well.  Medians
 with the min-max spread over the blocks.  ``--route NAME`` runs one route alone (for a
 kernel trace: ``rocprofv3 --kernel-trace --stats -- python tools/disent_step_timing.py
---route replay``).
+--route replay``).  ``--e2e-engine factorised`` times the model with the factorised training
+structure decoder (``snd_e2e_train``); ``--e2e-engine both`` alternates every route under
+both engines in one process (names ``route:engine``).
 
     python tools/disent_step_timing.py --out profiles/disent_step_timing.json
+    python tools/disent_step_timing.py --e2e-engine both --out profiles/disent_step_timing_engines.json
 """
 import argparse
 import json
@@ -41,11 +44,12 @@ def stats(v):
 
 
 class Route:
-    def __init__(self, name, cfg, blocks, batch, seed):
+    def __init__(self, name, cfg, blocks, batch, seed, engine="direct", label=None):
         from snd_vae_amd.disent_model import DisentangledSGCNModelVAE
         from snd_vae_amd.disent_trainer import eps_shapes
         self.name, self.seed, self.t, self.batch = name, seed, 0, batch
-        self.model = DisentangledSGCNModelVAE(cfg, B, blocks=blocks)
+        self.engine, self.label = engine, label or name
+        self.model = DisentangledSGCNModelVAE(cfg, B, blocks=blocks, e2e_engine=engine)
         self.eps = {k: torch.empty(*s, device="cuda") for k, s in eps_shapes(cfg, B).items()}
         self.graph, self.events = None, []
         if name == "replay":
@@ -98,6 +102,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="steps per block")
     ap.add_argument("--blocks", type=int, default=10, help="timed blocks per route")
     ap.add_argument("--warmup", type=int, default=2, help="untimed blocks per route")
+    ap.add_argument("--e2e-engine", choices=("direct", "factorised", "both"), default="direct",
+                    help="the training structure decoder of the timed model")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -109,25 +115,32 @@ def main():
     assert (cfg.n_nodes, cfg.sampling_num) == (N, S)
     batch = DeviceDisentBatch(sgjoint_batch(sgjoint(N, cfg.node_h, mean_degree=4.0, sampling_num=S), B, seed=3))
     blocks = init_blocks(cfg, 0)
-    routes = [Route(r, cfg, blocks, batch, seed=1234) for r in (ROUTES if a.route is None else (a.route,))]
+    engines = ("direct", "factorised") if a.e2e_engine == "both" else (a.e2e_engine,)
+    routes = [Route(r, cfg, blocks, batch, seed=1234, engine=e, label=r if a.e2e_engine == "direct" else f"{r}:{e}")
+              for r in (ROUTES if a.route is None else (a.route,)) for e in engines]
     for _ in range(a.warmup):
         for r in routes:
             r.block(a.steps)
-    wall = {r.name: [] for r in routes}
+    wall = {r.label: [] for r in routes}
     for _ in range(a.blocks):
         for r in routes:                                             # alternating
-            wall[r.name].append(r.block(a.steps, events=True))
+            wall[r.label].append(r.block(a.steps, events=True))
     res = {"shape": {"n_nodes": N, "sampling_num": S, "n_graphs": B, "model_type": cfg.model_type,
                      "param_count": routes[0].model.param_count},
            "steps_per_block": a.steps, "blocks": a.blocks, "device": torch.cuda.get_device_name(0),
            "wall_us_per_step": {k: stats(v) for k, v in wall.items()}}
     for r in routes:
         if r.events:
-            res["replay_event_us"] = stats([x.elapsed_time(y) * 1e3 for x, y in r.events])
+            key = "replay_event_us" if a.e2e_engine == "direct" else f"replay_event_us:{r.engine}"
+            res[key] = stats([x.elapsed_time(y) * 1e3 for x, y in r.events])
     # the device routes took the same steps from the same blocks and normals: the same last loss
-    res["last_cost"] = {r.name: float(r.model.losses[LOSS_NAMES.index("cost")]) for r in routes
+    # (per engine: the two engines sum in different orders)
+    res["last_cost"] = {r.label: float(r.model.losses[LOSS_NAMES.index("cost")]) for r in routes
                         if r.name != "eager"}
-    assert len(set(res["last_cost"].values())) <= 1, res["last_cost"]
+    for e in engines:
+        same = {v for r, v in zip(routes, [res["last_cost"].get(r.label) for r in routes])
+                if r.engine == e and r.name != "eager"}
+        assert len(same) <= 1, res["last_cost"]
     line = json.dumps(res)
     print(line)
     if a.out:
