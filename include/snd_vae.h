@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 24
+#define SND_ABI_VERSION 25
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -662,6 +662,45 @@ size_t snd_margin_eval_workspace(int n_graphs, int n);
 int snd_margin_eval(const float* margin, const float* adj, int n_graphs, int n,
                     long long* hist, long long* counts, int accumulate,
                     void* workspace, size_t workspace_bytes, snd_stream_t stream);
+
+/* ---- disentanglement evaluation: latent-factor mutual information (ABI 25) ----
+ * snd_latent_mi: the matrix of mutual information between every latent dimension and every
+ * generative factor, estimated from joint histograms: the object MIG, avgMI and modularity
+ * are host arithmetic on (metrics.LatentMI).  z [rows, n_lat] fp32 (row stride ldz >= n_lat)
+ * holds one row per graph, the encoder means; f [rows, n_fac] fp32 (row stride ldf >= n_fac)
+ * the generative factors, integer-coded ones passed as floats.  Any pointer alignment.
+ *   Range.  Per column of z and of f: lo = min, hi = max over the rows (order-free, so
+ *     deterministic; +-0 may come out with either sign).
+ *   Bin.  Every value v goes to
+ *       b = (hi > lo) ? min(nb - 1, (int)floor(((double)v - (double)lo) * nb / ((double)hi - (double)lo))) : 0
+ *     evaluated in double, left to right; nb = nbz for a latent column, nbf for a factor
+ *     column.  NumPy float64 on the same fp32 inputs gives the same bin, bit for bit (IEEE
+ *     subtraction, multiplication and division on both sides, nothing to contract into an
+ *     FMA).  k equally spaced factor values land in k distinct bins when nbf = k:
+ *     floor(i k / (k - 1)) = i for i < k - 1, and the maximum is clamped to k - 1.  A
+ *     constant column is all bin 0.  NaN inputs are unspecified (no fault, no write outside
+ *     the outputs).
+ *   Count and reduce.  joint[l][k][a][b] = #rows with bin(z[:, l]) = a and bin(f[:, k]) = b
+ *     (int32).  With r, s the marginals of a joint block, natural logs, in double, summed in
+ *     index order (a major, b minor):
+ *       mi[l][k] = sum_{a,b: c > 0} (c / rows) log(c rows / (r_a s_b))
+ *       hz[l] = - sum_a (r_a / rows) log(r_a / rows),   hf[k] likewise.
+ * Outputs (device): mi [n_lat, n_fac], hz [n_lat], hf [n_fac] doubles; range
+ * [n_lat + n_fac, 2] floats {lo, hi}, latent columns first (may be NULL); joint
+ * [n_lat, n_fac, nbz, nbf] int32 (may be NULL: the counts then live in the workspace).
+ * Counting is integer only (32-bit LDS and global atomics); there are no floating-point
+ * atomics: two runs are bitwise equal, and a captured-graph replay equals an eager call.
+ * No allocation, no host synchronisation.  workspace >= snd_latent_mi_workspace() bytes (0
+ * for a bad shape): the row slices' ranges, the ranges and the joint counts.
+ * SND_ERR_ARG before anything is launched: a NULL z, f, mi, hz or hf; rows < 1; n_lat not in
+ * [1, 65536]; n_fac not in [1, 64]; nbz or nbf not in [1, 32]; ldz < n_lat; ldf < n_fac; a
+ * short (or NULL) workspace. */
+size_t snd_latent_mi_workspace(int rows, int n_lat, int n_fac, int nbz, int nbf);
+int snd_latent_mi(const float* z, int ldz, const float* f, int ldf,
+                  int rows, int n_lat, int n_fac, int nbz, int nbf,
+                  double* mi, double* hz, double* hf,
+                  float* range, int* joint,
+                  void* workspace, size_t workspace_bytes, snd_stream_t stream);
 
 /* ---- a14: the whole train step (main.py:315-334) ---------------------------
  * A plan fixes shapes; the step runs forward + backward of the SND-VAE

@@ -17,7 +17,7 @@ c_int, c_ll, c_float, c_size, c_ull = C.c_int, C.c_longlong, C.c_float, C.c_size
 vp = C.c_void_p
 
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 GEN_MODES = {"sample": 0, "mean": 1, "prior": 2, "given": 3}
 TOPOLOGY = {"tscale": 0, "tref": 1, "sgjoint": 2}
 
@@ -154,6 +154,9 @@ _SIGS = {
     "snd_disent_losses": (c_int, [vp, c_int, C.c_double, vp, c_int, C.c_double, vp, C.c_double, vp, vp, vp, vp, vp]),
     "snd_margin_eval_workspace": (c_size, [c_int, c_int]),
     "snd_margin_eval": (c_int, [vp, vp, c_int, c_int, vp, vp, c_int, vp, c_size, vp]),
+    "snd_latent_mi_workspace": (c_size, [c_int, c_int, c_int, c_int, c_int]),
+    "snd_latent_mi": (c_int, [vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp,
+                              c_size, vp]),
     "snd_latent_reg_workspace": (c_size, [c_int, c_int]),
     "snd_latent_reg": (c_int, [vp, vp, vp, c_int, c_int, C.POINTER(LatentReg), vp, vp, vp, vp, vp]),
     "snd_bn_act_fwd": (c_int, [vp, c_int, c_ll, c_int, vp, vp, c_int, c_int, vp, c_int, vp]),

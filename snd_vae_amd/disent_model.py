@@ -547,6 +547,34 @@ class DisentangledSGCNModelVAE:
                 out[name]["z"] = ops.reparam_kl(ms, e)[0]
         return out
 
+    def latent_groups_columns(self) -> Dict[str, slice]:
+        """The column slices of ``latent_means``: {'s', 'g', 'sg'} in that order."""
+        cfg = self.cfg
+        a, b = cfg.s_latent, cfg.s_latent + cfg.g_latent
+        return {"s": slice(0, a), "g": slice(a, b), "sg": slice(b, b + cfg.sg_latent)}
+
+    def latent_means(self, batch: "DeviceDisentBatch", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The means of ``encode(batch)`` as one matrix [B, Ls + Lg + Lsg], columns in the
+        order s, g, sg, the sg copies of a graph averaged as ``mean_over_copies`` does
+        (main.py:407): what main.py:424 hands to disentangle_evaluation.  Written into
+        ``out`` when one is given (float32, [B, Ls + Lg + Lsg], unit column stride: a row
+        block of a caller-owned device matrix).  No read-back."""
+        cfg = self.cfg
+        B = self._n_graphs(batch)
+        cols = self.latent_groups_columns()
+        width = cols["sg"].stop
+        if out is None:
+            out = torch.empty(B, width, device=self.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, width)
+                  and (width == 1 or out.stride(1) == 1)):
+            raise ValueError(f"latent_means: out must be a float32 device tensor [{B}, {width}] with unit "
+                             "column stride")
+        enc = self.encode(batch)
+        out[:, cols["s"]] = enc["s"]["mu"]
+        out[:, cols["g"]] = enc["g"]["mu"]
+        out[:, cols["sg"]] = mean_over_copies(enc["sg"]["mu"], cfg.sampling_num)
+        return out
+
     def decode(self, z_s, z_sg, z_g, want_margin: bool = False) -> Dict[str, torch.Tensor]:
         """decoder(z_s, z_sg, z_g) of model.py:172-222 for any number of graphs B (not tied
         to the constructor's n_graphs): z_s [B, Ls], z_g [B, Lg], z_sg [B * S', Lsg] with J_sg

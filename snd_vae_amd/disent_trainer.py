@@ -63,6 +63,24 @@ def draw_step_eps(seed: int, t: int, out: Dict[str, torch.Tensor]) -> Dict[str, 
     return out
 
 
+def dataset_factors(dataset: SynDataset, n_graphs: Optional[int] = None) -> np.ndarray:
+    """``dataset.factor`` as float32 [n_graphs, K] (every graph by default), for
+    ``evaluate_disentanglement``.  ValueError when the dataset has no factors, when they are
+    not 2-D, or when their row count differs from the dataset's graphs: a test split reads
+    the training split's factor file (`input_data.py:101`), and no alignment is guessed."""
+    f = dataset.factor
+    if f is None:
+        raise ValueError("the dataset has no generative factors (2D_prop.npy was absent)")
+    f = np.asarray(f)
+    if f.ndim != 2 or f.shape[1] < 1:
+        raise ValueError(f"dataset.factor must be [n_graphs, K], got shape {f.shape}")
+    if f.shape[0] != dataset.n_graphs:
+        raise ValueError(f"dataset.factor has {f.shape[0]} rows for {dataset.n_graphs} graphs (a test split "
+                         "carries the training split's factors, input_data.py:101); no alignment is guessed")
+    n = dataset.n_graphs if n_graphs is None else n_graphs
+    return np.ascontiguousarray(f[:n], dtype=np.float32)
+
+
 class DisentTrainer:
     def __init__(self, cfg: DisentangledConfig, dataset: SynDataset, batch_size: int, seed: int = 1234,
                  use_graphs: bool = False, blocks=None, device="cuda", c_max: Optional[float] = None,
@@ -84,6 +102,7 @@ class DisentTrainer:
             for i in range(self.batch_num)]
         self.model = DisentangledSGCNModelVAE(cfg, batch_size, blocks=blocks, seed=seed, device=device,
                                               e2e_engine=e2e_engine)
+        self.dataset = dataset                # evaluate_disentanglement reads dataset.factor
         self.eps = {k: torch.empty(*shp, device=device) for k, shp in eps_shapes(cfg, batch_size).items()}
         self.use_graphs = use_graphs
         self.c_max, self.c_step, self.c_stop_iter = c_max, c_step, c_stop_iter
@@ -262,4 +281,32 @@ class DisentTrainer:
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         out = data.compare(gen)
         out.update(dataset=data, generated=gen, threshold=threshold, generated_csr=csr)
+        return out
+
+    def evaluate_disentanglement(self, n_bins: int = 20, factor_bins: Optional[int] = None) -> dict:
+        """Does each latent group capture its own generative factor?  (disentangle_evaluation,
+        `main.py:424`.)  The encoder means of every batch (``model.latent_means``: columns s,
+        g, sg, the sg copies averaged) fill one device matrix [batch_num * batch_size, L];
+        ``dataset.factor`` of the same graphs (the leftover graphs past the last whole batch
+        are excluded, as in training) is uploaded once, and one ``layers.latent_mi`` call
+        bins both (``n_bins`` per latent, ``factor_bins`` per factor, default n_bins) and
+        leaves the mutual-information matrix on the device.
+
+        Returns ``metrics.LatentMI.summary()`` (mig, avg_mi, modularity, group_share,
+        best_latent: this project's definitions, see LatentMI) plus the LatentMI under
+        "latent_mi", read back once.  Forward passes only; parameters, Adam state and the step
+        counter are not written.  ValueError when the dataset's factors are missing, not 2-D or
+        not one row per graph (``dataset_factors``)."""
+        from .metrics import LatentMI
+        rows = self.batch_num * self.batch_size
+        factors = dataset_factors(self.dataset, rows)
+        dev = self.model.params.device
+        cols = self.model.latent_groups_columns()
+        z = torch.empty(rows, cols["sg"].stop, device=dev)
+        for i, b in enumerate(self.batches):
+            self.model.latent_means(b, out=z[i * self.batch_size:(i + 1) * self.batch_size])
+        f = torch.from_numpy(factors).to(dev)
+        res = LatentMI(*layers.latent_mi(z, f, n_bins=n_bins, factor_bins=factor_bins), groups=cols)
+        out = res.summary()
+        out["latent_mi"] = res
         return out

@@ -321,3 +321,64 @@ def write_synthetic_dataset(path: str, cfg: SNDConfig, n_graphs: int, seed: int 
                 np.sqrt(((geometry[:, :, None] - geometry[:, None]) ** 2).sum(-1)))
     np.save(os.path.join(d, "2D_prop.npy"), np.arange(n_graphs, dtype=np.float64)[:, None])
     return d
+
+
+FACTOR_NAMES = ("spatial", "graph", "joint")    # the columns of write_factor_dataset's 2D_prop.npy
+
+
+def factor_graph(cfg: SNDConfig, levels: Sequence[int], seed: int):
+    """One graph of ``write_factor_dataset``: a pure function of (seed, levels), with levels =
+    (spatial, graph, joint).  Every random draw (positions, node attributes, the order in
+    which extra edges are tried) is made from ``default_rng(seed)`` before a level is looked
+    at, so changing one level changes only what that factor controls:
+
+    * joint: the RGG radius r0 (1 + level / 4), r0 = sqrt(mean_degree / (pi N)): which nodes
+      are joined depends on where they lie;
+    * graph: ``level`` extra edges, the first pairs of a random order of all pairs that are
+      not joined yet: topology only, blind to position;
+    * spatial: the coordinates scaled about the centre of the unit cube by 0.5 + 0.1 level,
+      after the edges are chosen: geometry only.
+
+    Returns (adj bool [N, N], coordinates [N, spatial_dim], node attributes [N, num_feature])."""
+    ls, lg, lsg = (int(v) for v in levels)
+    n, sd = cfg.n_nodes, cfg.spatial_dim
+    rng = np.random.default_rng(seed)
+    pos = rng.random((n, sd))
+    x = rng.random((n, cfg.num_feature))
+    iu, ju = np.triu_indices(n, 1)
+    order = rng.permutation(len(iu))
+    radius = np.sqrt(cfg.mean_degree / (np.pi * n)) * (1.0 + lsg / 4.0)
+    dist = np.sqrt(((pos[:, None] - pos[None]) ** 2).sum(-1))
+    adj = dist < radius
+    np.fill_diagonal(adj, False)
+    free = order[~adj[iu[order], ju[order]]][:lg]
+    adj[iu[free], ju[free]] = adj[ju[free], iu[free]] = True
+    coords = 0.5 + (pos - 0.5) * (0.5 + 0.1 * ls)
+    return adj, coords, x
+
+
+def write_factor_dataset(path: str, cfg: SNDConfig, n_graphs: int, seed: int = 0, levels: int = 5,
+                         split: str = "train", with_rel: bool = True) -> str:
+    """Write graphs with three independent generative factors (FACTOR_NAMES) in the reference
+    directory layout, for the disentanglement evaluation: 2D_prop.npy is [G, 3], each column
+    drawn uniformly from range(levels) per graph from ``seed``; graph g is
+    ``factor_graph(cfg, 2D_prop[g], seed + 1 + g)``.  Values are scaled back by 120 / 600 so
+    ``load_data_syn(load_rel=True)`` recovers the generator's; the adjacency is written as
+    2D_adj.npz and, with ``with_rel``, the pairwise distances of the written geometry as
+    2D_rel.npy."""
+    if levels < 1 or n_graphs < 1:
+        raise ValueError(f"write_factor_dataset: levels={levels} and n_graphs={n_graphs} must be >= 1")
+    n = cfg.n_nodes
+    d = os.path.join(path, split)
+    os.makedirs(d, exist_ok=True)
+    factor = np.random.default_rng(seed).integers(0, levels, size=(n_graphs, len(FACTOR_NAMES)))
+    graphs = [factor_graph(cfg, factor[g], seed + 1 + g) for g in range(n_graphs)]
+    save_adj_npz(os.path.join(d, "2D_adj.npz"), [csr_from_dense(a) for a, _, _ in graphs], n)
+    np.save(os.path.join(d, "2D_node.npy"), np.stack([x for _, _, x in graphs]) * NODE_SCALE)
+    geometry = np.stack([c for _, c, _ in graphs]) * COORD_SCALE
+    np.save(os.path.join(d, "2D_geometry.npy"), geometry)
+    if with_rel:
+        np.save(os.path.join(d, "2D_rel.npy"),
+                np.sqrt(((geometry[:, :, None] - geometry[:, None]) ** 2).sum(-1)))
+    np.save(os.path.join(d, "2D_prop.npy"), factor.astype(np.float64))
+    return d

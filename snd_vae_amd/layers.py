@@ -353,6 +353,58 @@ def graph_stats(rowptr, colidx, n_graphs, n, coords=None, max_len=None, hist=Non
     return (hist, totals, deg, tri2) if per_node else (hist, totals)
 
 
+def latent_mi(z, factors, n_bins=20, factor_bins=None, want_joint=False):
+    """Mutual information between every latent dimension and every generative factor
+    (snd_latent_mi), from joint histograms counted on chip; nothing is read back.
+
+    z: float32 device tensor [rows, L] (one row per graph, the encoder means), factors:
+    float32 device tensor [rows, K] on the same device (integer-coded factors as floats),
+    both with unit column stride; 1 <= L <= 65536, 1 <= K <= 64.  Every column is cut into
+    equal-width bins between its minimum and maximum: ``n_bins`` for a latent column,
+    ``factor_bins`` (default ``n_bins``) for a factor column, 1 to 32 each; k equally spaced
+    factor levels fill k bins at factor_bins = k.  Returns float64 device tensors (mi [L, K]
+    in nats, hz [L], hf [K]) (metrics.LatentMI turns them into MIG, avgMI, modularity ...);
+    with ``want_joint`` also (joint, range): the int32 counts [L, K, n_bins, factor_bins] and
+    the float32 [L + K, 2] {lo, hi} of the columns, latent ones first.  The counts are exact
+    and the result is bitwise repeatable.  No host synchronisation."""
+    for t, name in ((z, "z"), (factors, "factors")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] >= 1
+                and (t.shape[1] == 1 or t.stride(1) == 1)):
+            raise ValueError(f"latent_mi {name}: expected a float32 device tensor [rows, columns] with unit "
+                             "column stride")
+    rows, n_lat = z.shape
+    n_fac = factors.shape[1]
+    if factors.shape[0] != rows or factors.device != z.device:
+        raise ValueError(f"latent_mi: z has {rows} rows on {z.device}, factors {factors.shape[0]} on {factors.device}")
+    if n_lat > 65536 or n_fac > 64:
+        raise ValueError(f"latent_mi: at most 65536 latent and 64 factor columns, got {n_lat} and {n_fac}")
+    nbz = n_bins
+    nbf = n_bins if factor_bins is None else factor_bins
+    for nb, name in ((nbz, "n_bins"), (nbf, "factor_bins")):
+        if int(nb) != nb or not 1 <= nb <= 32:
+            raise ValueError(f"latent_mi: {name} must be an integer in [1, 32], got {nb!r}")
+    nbz, nbf = int(nbz), int(nbf)
+    ldz = z.stride(0) if rows > 1 else max(n_lat, z.stride(0))
+    ldf = factors.stride(0) if rows > 1 else max(n_fac, factors.stride(0))
+    if ldz < n_lat or ldf < n_fac:
+        raise ValueError("latent_mi: rows overlap (row stride below the number of columns)")
+    dev = z.device
+    out = torch.empty(n_lat * n_fac + n_lat + n_fac, dtype=torch.float64, device=dev)
+    mi, hz, hf = out[:n_lat * n_fac].view(n_lat, n_fac), out[n_lat * n_fac:n_lat * n_fac + n_lat], out[-n_fac:]
+    joint = rng = None
+    if want_joint:
+        joint = torch.empty(n_lat, n_fac, nbz, nbf, dtype=torch.int32, device=dev)
+        rng = torch.empty(n_lat + n_fac, 2, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    wsb = L.snd_latent_mi_workspace(rows, n_lat, n_fac, nbz, nbf)
+    if wsb == 0:
+        raise _lib.SNDError(f"snd_latent_mi_workspace: bad shape rows={rows} L={n_lat} K={n_fac} bins {nbz}, {nbf}")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(L.snd_latent_mi(_P(z), ldz, _P(factors), ldf, rows, n_lat, n_fac, nbz, nbf, _P(mi), _P(hz), _P(hf),
+                               _P(rng), _P(joint), _P(ws), wsb, _lib.stream_ptr()), "snd_latent_mi")
+    return (mi, hz, hf, joint, rng) if want_joint else (mi, hz, hf)
+
+
 def dense_to_csr(adj):
     """Reference dense adj_truth [B,N,N] -> (rowptr, colidx) on the device."""
     b, n, _ = adj.shape

@@ -16,6 +16,10 @@ clustering and edge-length histograms per graph from ``snd_graph_stats``, and th
 two-sample statistics (MMD with an EMD kernel, KL divergence) between a set of
 generated graphs and the data.
 
+``LatentMI`` (at the end) is the disentanglement side (`main.py:424`): MIG, avgMI,
+modularity and the per-group share of each factor's information, from the
+latent-factor mutual-information matrix of ``snd_latent_mi``.
+
 Pure NumPy: imports without a GPU.  torch is imported only when a device tensor
 or a process group is handed in.
 """
@@ -509,3 +513,176 @@ class GraphStats:
 
     def __repr__(self) -> str:
         return f"GraphStats(n_graphs={self.n_graphs}, n={self.n}, max_len={self.max_len})"
+
+
+class LatentMI:
+    """mi [L, K], hz [L] and hf [K] of ``layers.latent_mi`` / ``snd_latent_mi``: the mutual
+    information (nats) between every latent dimension and every generative factor and the
+    entropies of their binned marginals, the third of the reference's evaluations
+    (``disentangle_evaluation``, `main.py:424`).
+
+    The reference's own ``utils/evaluation.py`` is not shipped, so the scores below are this
+    project's definitions, each from the paper its docstring cites; all of them are host
+    arithmetic on the matrix R[l, k] = mi[l, k] / hf[k] (0 where hf[k] = 0: a factor that
+    never varies carries no information).  Built from NumPy arrays or from three float64
+    torch tensors; device tensors are read back once, on first use.
+
+    ``groups`` maps group names to the column slices of the latent axis, in display order:
+    ``{"s": slice(0, Ls), "g": slice(Ls, Ls + Lg), "sg": slice(Ls + Lg, L)}`` for the
+    disentangled model (``DisentangledSGCNModelVAE.latent_means``); None is one group "z".
+    """
+
+    def __init__(self, mi, hz, hf, groups=None):
+        self._dev = None
+        self._np = None
+        if _is_tensor(mi):
+            if mi.dim() != 2 or tuple(hz.shape) != (mi.shape[0],) or tuple(hf.shape) != (mi.shape[1],):
+                raise ValueError("LatentMI: expected mi [L, K], hz [L] and hf [K]")
+            self._dev = (mi, hz, hf)
+            L = int(mi.shape[0])
+        else:
+            m, a, b = (np.asarray(x, dtype=np.float64) for x in (mi, hz, hf))
+            if m.ndim != 2 or a.shape != (m.shape[0],) or b.shape != (m.shape[1],):
+                raise ValueError("LatentMI: expected mi [L, K], hz [L] and hf [K]")
+            self._np = (m, a, b)
+            L = m.shape[0]
+        if L < 1 or (self._dev[0] if self._np is None else self._np[0]).shape[1] < 1:
+            raise ValueError("LatentMI: expected at least one latent and one factor")
+        if groups is None:
+            groups = {"z": slice(0, L)}
+        self.groups = {}
+        seen = np.zeros(L, np.int64)
+        for name, sl in groups.items():
+            if not isinstance(sl, slice):
+                raise ValueError(f"LatentMI: groups[{name!r}] must be a slice")
+            lo, hi, step = sl.indices(L)
+            if step != 1 or hi <= lo:
+                raise ValueError(f"LatentMI: groups[{name!r}] = {sl} is empty or strided over {L} latents")
+            self.groups[str(name)] = slice(lo, hi)
+            seen[lo:hi] += 1
+        if not np.all(seen == 1):
+            raise ValueError(f"LatentMI: the groups must cover each of the {L} latents exactly once")
+
+    # ---- storage
+    @property
+    def tensors(self):
+        """The (mi, hz, hf) torch tensors this object was built on, or None."""
+        return self._dev
+
+    def invalidate(self) -> None:
+        """Forget the host copy: the device tensors were written since it was read."""
+        if self._dev is not None:
+            self._np = None
+
+    def _arrays(self):
+        if self._np is None:
+            import torch
+            m, a, b = self._dev
+            both = torch.cat([m.reshape(-1), a.reshape(-1), b.reshape(-1)]).cpu().numpy()     # one read-back
+            L, K = m.shape
+            self._np = (both[:L * K].reshape(L, K), both[L * K:L * K + L], both[L * K + L:])
+        return self._np
+
+    @property
+    def mi(self) -> np.ndarray:
+        return self._arrays()[0]
+
+    @property
+    def hz(self) -> np.ndarray:
+        return self._arrays()[1]
+
+    @property
+    def hf(self) -> np.ndarray:
+        return self._arrays()[2]
+
+    @property
+    def n_latents(self) -> int:
+        return int((self._dev[0] if self._np is None else self._np[0]).shape[0])
+
+    @property
+    def n_factors(self) -> int:
+        return int((self._dev[0] if self._np is None else self._np[0]).shape[1])
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, LatentMI) and self.groups == other.groups and np.array_equal(self.mi, other.mi)
+                and np.array_equal(self.hz, other.hz) and np.array_equal(self.hf, other.hf))
+
+    __hash__ = None
+
+    # ---- scores
+    def normalised(self) -> np.ndarray:
+        """R[l, k] = mi[l, k] / hf[k], 0 where hf[k] = 0 (the normalisation of Chen et al.
+        2018, eq. 6: I(z_l; v_k) / H(v_k) lies in [0, 1])."""
+        hf = self.hf
+        return np.divide(self.mi, hf[None, :], out=np.zeros_like(self.mi), where=hf[None, :] > 0)
+
+    def mig(self) -> float:
+        """Mutual information gap (Chen et al. 2018, "Isolating Sources of Disentanglement
+        in VAEs", eq. 6; this project's statement of it): per factor the largest R[:, k]
+        minus the second largest (0 for the second when there is one latent), averaged over
+        the factors with hf > 0.  NaN when no factor varies.  Higher is better; 1 when
+        every factor is copied by exactly one latent."""
+        R, live = self.normalised(), self.hf > 0
+        if not live.any():
+            return NAN
+        top = np.sort(R[:, live], axis=0)[::-1]
+        second = top[1] if top.shape[0] > 1 else np.zeros_like(top[0])
+        return float(np.mean(top[0] - second))
+
+    def avg_mi(self) -> float:
+        """avgMI as the SND-VAE / NED-VAE papers use it (Guo et al. 2020, "Interpretable
+        Deep Graph Generation with Node-Edge Co-Disentanglement", and the SND-VAE paper's
+        Table; this project's statement): the squared distance of R from the one-to-one
+        assignment T, T[l, k] = 1 at l = argmax_l R[l, k] (the lowest index on a tie) and 0
+        elsewhere, sum (R - T)^2 / K.  Lower is better; 0 when every factor is copied by one
+        latent and known to no other."""
+        R = self.normalised()
+        T = np.zeros_like(R)
+        T[np.argmax(R, axis=0), np.arange(R.shape[1])] = 1.0
+        return float(np.sum((R - T) ** 2) / R.shape[1])
+
+    def modularity(self) -> float:
+        """Modularity (Ridgeway and Mozer 2018, "Learning Deep Disentangled Embeddings with
+        the F-Statistic Loss", eq. 2-3; this project's statement): per latent with
+        theta = max_k mi[l, k]^2 > 0 the value 1 - sum_{k != k*} mi[l, k]^2 / (theta (K - 1)),
+        averaged over those latents; 1 when K = 1, NaN when no latent has any information.
+        1 when every latent knows about one factor only."""
+        m2 = self.mi ** 2
+        K = m2.shape[1]
+        if K == 1:
+            return 1.0
+        theta = m2.max(axis=1)
+        live = theta > 0
+        if not live.any():
+            return NAN
+        rest = m2[live].sum(axis=1) - theta[live]
+        return float(np.mean(1.0 - rest / (theta[live] * (K - 1))))
+
+    def group_share(self) -> np.ndarray:
+        """[K, groups]: the share of factor k's information held by each latent group,
+        sum_{l in group} mi[l, k] / sum_l mi[l, k] (0 where the denominator is 0), columns in
+        the order of ``groups``.  For the disentangled model this is the SND-VAE claim in one
+        table: does the spatial factor live in z_s, the graph factor in z_g, the joint one in
+        z_sg.  This project's definition."""
+        mi = self.mi
+        tot = mi.sum(axis=0)
+        part = np.stack([mi[sl].sum(axis=0) for sl in self.groups.values()], axis=1)
+        return np.divide(part, tot[:, None], out=np.zeros_like(part), where=tot[:, None] > 0)
+
+    def best_latent(self):
+        """Per factor the (group, index within the group) of the latent with the largest
+        R[:, k] (the lowest index on a tie)."""
+        out = []
+        for l in np.argmax(self.normalised(), axis=0):
+            for name, sl in self.groups.items():
+                if sl.start <= l < sl.stop:
+                    out.append((name, int(l - sl.start)))
+        return out
+
+    def summary(self) -> dict:
+        return {"mig": self.mig(), "avg_mi": self.avg_mi(), "modularity": self.modularity(),
+                "group_share": self.group_share(), "best_latent": self.best_latent(),
+                "groups": list(self.groups)}
+
+    def __repr__(self) -> str:
+        return f"LatentMI(latents={self.n_latents}, factors={self.n_factors}, groups={list(self.groups)})"
