@@ -12,33 +12,24 @@
 //   edge kernel (snd_spmm.hip): the A-weighted terms over the CSR only.
 // so the adjacency never enters the O(N^2 d) kernel.
 //
-// Dense kernel structure (flash-style, no softmax normalisation needed):
-//   workgroup = 8 waves x 16 rows i (128 rows of one graph); column tiles of
-//   64 j staged in LDS twice -- z rows (K role) and z^T (V role) -- double
-//   buffered, one barrier per tile.  Per 32-column chunk each wave runs
-//   MFMA1  X[j,i] = z_j . z_i           (16x16x32 bf16, z_i held in VGPRs)
-//   VALU   sigma / softplus / count on X (exp2 + rcp; one log2 per 8 logits
-//          via the product identity sum log(1+e_k) = log prod(1+e_k))
-//   MFMA2  dJd^T[c,i] += z^T[c,j] sigma[j,i]  -- the f32 accumulator X is
-//          re-packed to bf16 in registers and used as the B operand directly
-//          (no LDS round trip; k order permuted to match).
-// z is pre-scaled by sqrt(log2 e) for the K role, so X = L log2(e) feeds
-// v_exp_f32 (2^x) with no multiply.  LDS images are XOR-swizzled so the
-// ds_read_b128 (K role) and ds_read_b64 (V role) operand reads are
-// bank-conflict-free.  Block -> (graph, row block) puts one graph's blocks on
-// one XCD when B % 8 == 0 (blockIdx % 8 == graph % 8), so a graph's z stays
-// in that XCD's L2.
-// fp32 parity mode uses the exact-f32 MFMA 16x16x4 with the same structure.
+// The dense kernel per (dtype, padded width dp = zzt_dp(d)); launch_zzt_dense picks it,
+// each kernel's header comment below describes its structure:
+//   bf16, dp = 32    zzt_dense_bf16_v4<32>  1024 threads, 32x32x16 MFMAs, signed epilogue
+//   bf16, dp = 64    zzt_dense_bf16_v9      v4's per-wave work, two 512-thread workgroups per CU
+//   bf16, dp = 128   zzt_dense_bf16_v7      v4's work split on one dual-use LDS image per tile
+//   bf16, any dp     zzt_dense_bf16<dp>     v1, ZztArgs.variant 1 only (the bench's previous variant)
+//   f32,  any dp     zzt_dense_f32<dp>      parity mode: v1's structure on the exact-f32 MFMA 16x16x4
+// The bf16 defaults have a measurement instantiation each (MEAS, variant >= 256).
+// Common to all: z is pre-scaled by sqrt(log2 e) for the K role (zzt_prep_kernel), so
+// X = L log2(e) feeds v_exp_f32 (2^x) with no multiply.  Block -> (graph, row block) puts
+// one graph's blocks on one XCD when B % 8 == 0 (blockIdx % 8 == graph % 8), so a graph's
+// z stays in that XCD's L2.
 #include "snd_zzt.hpp"
 
 #include <type_traits>
 #include "snd_spmm.hpp"
 
 #include <algorithm>
-
-#ifndef SND_ZZT_V9
-#define SND_ZZT_V9 1     // the d = 64 kernel: 1 v9 (two 512-thread workgroups per CU, round 5:
-#endif                   // 55.2 vs v4's 56.7 us), 0 v4, 2 v9 with v7's stagger (55.7 us); A/B builds
 
 namespace snd {
 namespace {
@@ -141,7 +132,19 @@ __device__ __forceinline__ void block_reduce_write(ChunkStats st, double* part) 
   }
 }
 
-// ---------------------------------------------------------------- bf16 MFMA
+// ---------------------------------------------------------------- bf16 MFMA, v1
+// v1 (flash-style, no softmax normalisation needed; ZztArgs.variant 1):
+//   workgroup = 8 waves x 16 rows i (128 rows of one graph); column tiles of
+//   64 j staged in LDS twice -- z rows (K role) and z^T (V role) -- double
+//   buffered, one barrier per tile.  Per 32-column chunk each wave runs
+//   MFMA1  X[j,i] = z_j . z_i           (16x16x32 bf16, z_i held in VGPRs)
+//   VALU   sigma / softplus / count on X (exp2 + rcp; one log2 per 8 logits
+//          via the product identity sum log(1+e_k) = log prod(1+e_k))
+//   MFMA2  dJd^T[c,i] += z^T[c,j] sigma[j,i]  -- the f32 accumulator X is
+//          re-packed to bf16 in registers and used as the B operand directly
+//          (no LDS round trip; k order permuted to match).
+// LDS images are XOR-swizzled so the ds_read_b128 (K role) and ds_read_b64 (V role)
+// operand reads are bank-conflict-free.
 template <int DP> struct Swz;
 template <> struct Swz<32> { static __device__ __forceinline__ int j(int) { return 0; } };
 template <> struct Swz<64> { static __device__ __forceinline__ int j(int row) { return (row >> 1) & 7; } };
@@ -280,6 +283,7 @@ constexpr int NTH2 = 1024;
 
 
 // ---------------------------------------------------------------- f32 MFMA
+// fp32 parity mode: v1's structure on the exact-f32 MFMA 16x16x4.
 __device__ __forceinline__ int hJ(int row) { return ((row & 1) << 1) | (((row >> 1) & 7) << 2); }
 __device__ __forceinline__ int hT(int c) { return (c & 3) | (((c >> 2) & 3) << 3); }
 
@@ -1075,7 +1079,7 @@ __global__ void __launch_bounds__(NTH2) zzt_dense_bf16_v7(ZztArgs a) {
 }
 
 
-// ---------------------------------------------------------------- bf16 MFMA, v9 (d <= 64, A/B)
+// ---------------------------------------------------------------- bf16 MFMA, v9 (d = 64)
 // v4's per-wave work (one 32 x 32 logit block per 128-column tile, the same signed
 // epilogue) in HALF-size workgroups -- 512 threads = 2 row groups (64 rows i) x 4
 // column blocks -- with v7's single dual-use LDS image per tile (16 KB at d = 64:
@@ -1086,7 +1090,8 @@ __global__ void __launch_bounds__(NTH2) zzt_dense_bf16_v7(ZztArgs a) {
 // workgroup leave every tile barrier together, so the matrix and vector phases add up
 // (DESIGN §5).  Tiles arrive by LDS-DMA into a 3-deep ring; the image holds
 // z * sqrt(log2 e) (v7), so the backward result is divided by sqrt(log2 e) once.
-// STAG: the odd column-block waves run one tile late (v7's stagger).
+// The tile loop: the workgroup's -z_i rows sit in an LDS image read again every tile;
+// tile t + 1's DMA is issued in tile t, a full vmcnt(0) drain and a barrier end each tile.
 constexpr int NTH9 = 512;
 constexpr int ROWS9 = 64;
 __device__ __forceinline__ int zoa64(int row, int ch) {   // [128][64] bf16 image, 16-byte chunk ch
@@ -1102,36 +1107,20 @@ __device__ __forceinline__ int zoa64(int row, int ch) {   // [128][64] bf16 imag
 //   and barrier, even tiles run their epilogue once and the backward MFMAs twice (what a
 //   J >= I tile kernel computes per logit block: forward 4 + epilogue + 2 x 4 backward
 //   MFMAs over half the blocks; DESIGN §5 "symmetric tiles, measured")
-//
-// LOOP: the tile loop (A/B: ZztArgs.variant & 255 = 9 + LOOP, zzt_dense_v9 .. v12; the
-// arithmetic and its order are the same in all four, the results bitwise equal) --
-//   0  round 5's: -z_i rows in LDS, read again every tile; tile t + 1's DMA issued in
-//      tile t, a full vmcnt(0) drain and a barrier per tile; 3 slots
-//   1  the wave's four -z_i operands held in registers (loaded once from the row image;
-//      no LDS copy of the rows), the loop as 0
-//   2  1 + the DMA two tiles ahead: tile t + 2 goes into tile t - 1's slot, the tile ends
-//      on a counted vmcnt(2) (tile t + 1 landed, t + 2 in flight) and a barrier; 3 slots
-//   3  1 + two-tile stages on a 4-slot ring: the next stage's two fills are issued at the
-//      stage's start, both tiles run with no barrier between them, then one drain and
-//      one barrier per stage (half of 0's), every fill has two tile times to land
-constexpr int kZztLoops = 4;
-constexpr int kZztLoopShipped = 0;
-constexpr int kZztLoopVariant0 = 9;    // ZztArgs.variant & 255 of LOOP 0
 typedef int zv4i __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void zkeep(const bf16x8& v) {   // MEAS: an operand read stays without its MFMA
   asm volatile("" ::"v"(__builtin_bit_cast(zv4i, v)));
 }
 
-template <bool STAG, bool MEAS, int LOOP>
+template <bool MEAS>
 __device__ __forceinline__ void zzt_v9_body(const ZztArgs& a) {
-  static_assert(!STAG || LOOP == 0, "the stagger's deferred backward reads tile t - 1's slot");
   constexpr int DP = 64, NT = NTH9, NW = NT / 64;
   const int skip = MEAS ? __builtin_amdgcn_readfirstlane(a.variant >> 8) : 0;
   constexpr int KS = DP / 16;          // forward k-steps
   constexpr int CB = DP / 32;          // backward 32-column output blocks
   constexpr int IMG = TJ2 * DP * 2;    // one [128][64] bf16 image, 16 KB
-  constexpr int NS = LOOP == 3 ? 4 : 3;                          // ring slots
-  constexpr int BROWS = LOOP == 0 ? ROWS9 * DP * 2 : 0;          // the -z_i rows' LDS image
+  constexpr int NS = 3;                // ring slots
+  constexpr int BROWS = ROWS9 * DP * 2;   // the -z_i rows' LDS image
   __shared__ __attribute__((aligned(16))) char lds[NS * IMG + BROWS];   // ring, -z_i rows
   __shared__ float colsum[DP];
   __shared__ float csred[NT / DP][DP];
@@ -1173,26 +1162,14 @@ __device__ __forceinline__ void zzt_v9_body(const ZztArgs& a) {
              __builtin_amdgcn_readfirstlane(lds0 + b * IMG + 1024 * (w + 8 * k)));
   };
 
-  // ---- prologue: tile t0 (LOOP >= 2: and t0 + 1) in flight; -z_i rows; column sums
+  // ---- prologue: tile t0 in flight; -z_i rows; column sums
   dma(t0, 0);
-  if (LOOP >= 2 && t0 + 1 < t1) dma(t0 + 1, 1);
   const int ja = 32 * cb + r, ia = 32 * rg + r;
-  bf16x8 bz[KS];   // LOOP >= 1: the forward B operands, k-step s = -z_i chunk 2 s + h
-  if constexpr (LOOP == 0) {
-    for (int idx = tid; idx < ROWS9 * (DP / 8); idx += NT) {
-      const int row = idx >> 3, ch = idx & 7;
-      const uint4 u = *reinterpret_cast<const uint4*>(Jg + (long long)(r0 + row) * DP + ch * 8);
-      *reinterpret_cast<uint4*>(brows + zoa64(row, ch)) =
-          make_uint4(u.x ^ 0x80008000u, u.y ^ 0x80008000u, u.z ^ 0x80008000u, u.w ^ 0x80008000u);
-    }
-  } else {
-    const uint4* src = reinterpret_cast<const uint4*>(Jg + (long long)(r0 + ia) * DP + 8 * h);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const uint4 u = src[2 * s];
-      bz[s] = __builtin_bit_cast(bf16x8, make_uint4(u.x ^ 0x80008000u, u.y ^ 0x80008000u,
-                                                    u.z ^ 0x80008000u, u.w ^ 0x80008000u));
-    }
+  for (int idx = tid; idx < ROWS9 * (DP / 8); idx += NT) {
+    const int row = idx >> 3, ch = idx & 7;
+    const uint4 u = *reinterpret_cast<const uint4*>(Jg + (long long)(r0 + row) * DP + ch * 8);
+    *reinterpret_cast<uint4*>(brows + zoa64(row, ch)) =
+        make_uint4(u.x ^ 0x80008000u, u.y ^ 0x80008000u, u.z ^ 0x80008000u, u.w ^ 0x80008000u);
   }
   {
     const int nrb = a.npad / 64;
@@ -1226,12 +1203,9 @@ __device__ __forceinline__ void zzt_v9_body(const ZztArgs& a) {
     for (int v = 0; v < 16; ++v) acc[q][v] = 0.f;
   // forward operand bases (k-step s: base[s & 1] + 512 (s >> 1))
   const int fa0 = zoa64(ja, h), fa1 = zoa64(ja, 2 + h);
-  const int fb0 = zoa64(ia, h), fb1 = zoa64(ia, 2 + h);   // LOOP 0
-  auto brow = [&](int s) {
-    if constexpr (LOOP == 0)
-      return *reinterpret_cast<const bf16x8*>(brows + ((s & 1) ? fb1 : fb0) + 512 * (s >> 1));
-    else
-      return bz[s];
+  const int fb0 = zoa64(ia, h), fb1 = zoa64(ia, 2 + h);
+  auto brow = [&](int s) {   // the forward B operand of k-step s: -z_i chunk 2 s + h
+    return *reinterpret_cast<const bf16x8*>(brows + ((s & 1) ? fb1 : fb0) + 512 * (s >> 1));
   };
   // backward transposed-read bases (v7's, 8-row groups of 1 KB): lane 4 qq + pp of group
   // gq supplies row 32 cb + 16 s + 8 t + 4 (gq >> 1) + qq, columns 32 q + 16 (gq & 1) + 4 pp
@@ -1305,27 +1279,18 @@ __device__ __forceinline__ void zzt_v9_body(const ZztArgs& a) {
         acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sA[s], bv, acc[q], 0, 0, 0);
       }
   };
-  auto run = [&](auto late_c) {
-    constexpr bool LATE = decltype(late_c)::value;
-    f32x16 Yp;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) Yp[v] = 0.f;
+  // the tile loop.  Tile t in ring slot CUR: tile t + 1's DMA into the slot tile t - 2
+  // left, forward, epilogue, backward; then the full drain (tile t + 1 landed) and the barrier.
+  // (run stays a lambda, and this body a function of its own under the kernel: written
+  // straight into the kernel the same code compiles to a different instruction order)
+  auto run = [&]() {
     auto tile = [&](int t, auto cc) {
-      constexpr int CUR = decltype(cc)::value, NN = (CUR + 2) % 3;
+      constexpr int CUR = decltype(cc)::value;
       if (t + 1 < t1) dma(t + 1, (CUR + 1) % 3);
-      if constexpr (LATE) {
-        if (t > t0) {
-          bf16x8 sA[2];
-          epi(Yp, sA);
-          bwd(NN, sA);   // tile t-1's slot
-        }
-        Yp = fwd(CUR);
-      } else {
-        const f32x16 Y = fwd(CUR);
-        bf16x8 sA[2];
-        epi(Y, sA);
-        bwd(CUR, sA);
-      }
+      const f32x16 Y = fwd(CUR);
+      bf16x8 sA[2];
+      epi(Y, sA);
+      bwd(CUR, sA);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile t+1 landed
       __syncthreads();
     };
@@ -1333,90 +1298,11 @@ __device__ __forceinline__ void zzt_v9_body(const ZztArgs& a) {
       tile(t, std::integral_constant<int, 0>{});
       if (t + 1 < t1) tile(t + 1, std::integral_constant<int, 1>{});
       if (t + 2 < t1) tile(t + 2, std::integral_constant<int, 2>{});
-      ltot += (double)lacc;
-      lacc = 0.f;
-    }
-    if (LATE && t1 > t0) {
-      bf16x8 sA[2];
-      epi(Yp, sA);
-      bwd((t1 - 1 - t0) % 3, sA);
-      ltot += (double)lacc;
+      ltot += (double)lacc;   // keep the fp32 partial sums short
       lacc = 0.f;
     }
   };
-  // one whole tile out of slot b
-  auto whole = [&](int b) {
-    const f32x16 Y = fwd(b);
-    bf16x8 sA[2];
-    epi(Y, sA);
-    bwd(b, sA);
-  };
-  // the end of a tile (LOOP 2) or stage (LOOP 3): this wave's fills landed, but for its
-  // last two pieces where a later tile is in flight; its LDS reads done; then the barrier
-  // (raw: the fills in flight are not drained)
-  auto tile_end = [&](bool two_in_flight) {
-    if (two_in_flight) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  // LOOP 2: tiles t and t + 1 issued before tile t starts; t + 2 goes into t - 1's slot,
-  // which every wave left at the barrier that ended t - 1
-  auto run_ahead2 = [&]() {
-    auto tile = [&](int t, auto cc) {
-      constexpr int CUR = decltype(cc)::value;
-      const bool more = t + 2 < t1;
-      if (more) dma(t + 2, (CUR + 2) % 3);
-      whole(CUR);
-      tile_end(more);   // tile t + 1 landed
-    };
-    for (int t = t0; t < t1; t += 3) {
-      tile(t, std::integral_constant<int, 0>{});
-      if (t + 1 < t1) tile(t + 1, std::integral_constant<int, 1>{});
-      if (t + 2 < t1) tile(t + 2, std::integral_constant<int, 2>{});
-      ltot += (double)lacc;
-      lacc = 0.f;
-    }
-  };
-  // LOOP 3: the stage of tiles t, t + 1 in slots S, S + 1; the next stage's fills go into
-  // the other pair, which every wave left at the barrier that ended the stage before.
-  // lacc is folded every third tile, as the one-tile loops do (the same sums, bitwise)
-  auto run_stages = [&]() {
-    int ph = 0;
-    auto one = [&](int b) {
-      whole(b);
-      if (++ph == 3) {
-        ltot += (double)lacc;
-        lacc = 0.f;
-        ph = 0;
-      }
-    };
-    auto stage = [&](int t, auto cc) {
-      constexpr int S = decltype(cc)::value;
-      if (t + 2 < t1) dma(t + 2, S ^ 2);
-      if (t + 3 < t1) dma(t + 3, (S ^ 2) + 1);
-      one(S);
-      if (t + 1 < t1) one(S + 1);
-      tile_end(false);   // the next stage landed
-    };
-    for (int t = t0; t < t1; t += 4) {
-      stage(t, std::integral_constant<int, 0>{});
-      if (t + 2 < t1) stage(t + 2, std::integral_constant<int, 2>{});
-    }
-    ltot += (double)lacc;
-    lacc = 0.f;
-  };
-  if constexpr (LOOP == 2) {
-    run_ahead2();
-  } else if constexpr (LOOP == 3) {
-    run_stages();
-  } else if (STAG && !MEAS && (cb & 1)) {
-    __builtin_amdgcn_s_setprio(1);
-    run(std::true_type{});
-    __builtin_amdgcn_s_setprio(0);
-  } else {
-    run(std::false_type{});
-  }
+  run();
 
   // ---- per-row corrections (row i_me; lanes r and r + 32 hold its two k halves)
   float xd = 0.f, xs = 0.f;
@@ -1506,18 +1392,10 @@ __device__ __forceinline__ void zzt_v9_body(const ZztArgs& a) {
   }
 }
 
-// the shipped kernel (the stagger build keeps loop 0: its deferred backward still reads
-// tile t - 1's slot, so it cannot prefetch two tiles ahead)
-template <bool STAG, bool MEAS>
+template <bool MEAS>
 __global__ void __launch_bounds__(NTH9) __attribute__((amdgpu_waves_per_eu(4, 4)))
 zzt_dense_bf16_v9(ZztArgs a) {
-  zzt_v9_body<STAG, MEAS, STAG ? 0 : kZztLoopShipped>(a);
-}
-// one named tile loop (A/B, ZztArgs.variant & 255 = 9 + LOOP)
-template <int LOOP, bool MEAS>
-__global__ void __launch_bounds__(NTH9) __attribute__((amdgpu_waves_per_eu(4, 4)))
-zzt_dense_bf16_v9_loop(ZztArgs a) {
-  zzt_v9_body<false, MEAS, LOOP>(a);
+  zzt_v9_body<MEAS>(a);
 }
 
 // dJd += sum of the column-split partials (fixed order)
@@ -1588,7 +1466,8 @@ int zzt_tsplit_blocks(int wgs, int n, int dtype) {
   // 0.1546 -> 0.1512 ms against 4 splits; B = 2 unchanged at 4)
   return std::max(1, std::min({cdiv(ncu, wgs), 8, ntiles}));
 }
-int zzt_wpb(int d, int dtype) { return (SND_ZZT_V9 && dtype == SND_BF16 && zzt_dp(d) == 64) ? 2 : 1; }
+// bf16 at dp = 64 is v9: two 64-row workgroups, and loss partials, per 128-row block
+int zzt_wpb(int d, int dtype) { return (dtype == SND_BF16 && zzt_dp(d) == 64) ? 2 : 1; }
 int zzt_dense_blocks(int ngraphs, int n, int d, int dtype) {
   return ngraphs * (zzt_npad(n) / ROWS) * zzt_tsplit(ngraphs, n, dtype) * zzt_wpb(d, dtype);
 }
@@ -1632,11 +1511,11 @@ int launch_zzt_dense(const ZztArgs& a, int dtype, hipStream_t s, bool defer_spli
   SND_CHECK_ARG(a.rb0 >= 0 && a.nrb >= 0 && a.rb0 + zrb(a) <= a.npad / ROWS,
                 "zzt_dense: row blocks [%d, %d) outside the %d of the graph", a.rb0, a.rb0 + zrb(a),
                 a.npad / ROWS);
-  // v9's named tile loops (variant & 255 = 9 .. 12): the default kernel with another loop
-  const int loop9 = (a.variant & 255) - kZztLoopVariant0;
-  const bool v9 = dtype == SND_BF16 && dp == 64 && SND_ZZT_V9;
-  const bool v9loop = v9 && loop9 >= 0 && loop9 < kZztLoops;
-  const int ts = (dtype == SND_BF16 && (a.variant == 0 || (v9loop && a.variant < 256)))
+  // 0 the (dtype, dp)'s kernel, 1 v1 (bf16), 256 * bits the default's measurement build
+  const bool meas = a.variant >= 256 && (a.variant & 255) == 0;
+  SND_CHECK_ARG(a.variant == 0 || a.variant == 1 || meas,
+                "zzt_dense: unknown variant %d (0, 1 or 256 * measurement bits)", a.variant);
+  const int ts = (dtype == SND_BF16 && a.variant == 0)
                      ? (a.tsplit > 0 ? a.tsplit : zzt_tsplit_blocks(a.ngraphs * zrb(a), a.n, dtype)) : 1;
   SND_CHECK_ARG(ts <= std::max(1, zzt_tsplit_blocks(a.ngraphs * zrb(a), a.n, dtype)),
                 "zzt_dense: %d column splits > the %d the scratch is sized for", ts,
@@ -1644,48 +1523,25 @@ int launch_zzt_dense(const ZztArgs& a, int dtype, hipStream_t s, bool defer_spli
   SND_CHECK_ARG(ts == 1 || a.dJd_extra, "zzt_dense: column splits need dJd_extra");
   SND_CHECK_ARG(a.nrb == 0 || a.ngraphs == 1, "zzt_dense: a row-block range needs one graph");
   dim3 grid(a.ngraphs * zrb(a) * ts);
-  if (dtype == SND_BF16 && a.variant == 1) {          // v1: 8 waves x 16 rows, TJ 64
-    if (dp == 32) hipLaunchKernelGGL((zzt_dense_bf16<32>), grid, dim3(NTH), 0, s, a);
-    else if (dp == 64) hipLaunchKernelGGL((zzt_dense_bf16<64>), grid, dim3(NTH), 0, s, a);
-    else hipLaunchKernelGGL((zzt_dense_bf16<128>), grid, dim3(NTH), 0, s, a);
-  } else if (v9loop) {                                // v9 with a named tile loop (A/B)
-    const dim3 g9(grid.x * 2);
-#define SND_V9_LOOP(LP)                                                                      \
-  case LP:                                                                                   \
-    if (a.variant >= 256)                                                                    \
-      hipLaunchKernelGGL((zzt_dense_bf16_v9_loop<LP, true>), g9, dim3(NTH9), 0, s, a);       \
-    else                                                                                     \
-      hipLaunchKernelGGL((zzt_dense_bf16_v9_loop<LP, false>), g9, dim3(NTH9), 0, s, a);      \
-    break
-    switch (loop9) {
-      SND_V9_LOOP(0);
-      SND_V9_LOOP(1);
-      SND_V9_LOOP(2);
-      SND_V9_LOOP(3);
-    }
-#undef SND_V9_LOOP
-  } else if (v9 && (a.variant == 0 || a.variant >= 256)) {   // v9
-    const dim3 g9(grid.x * 2);
-    if (a.variant >= 256) hipLaunchKernelGGL((zzt_dense_bf16_v9<false, true>), g9, dim3(NTH9), 0, s, a);
-    else if (SND_ZZT_V9 == 2) hipLaunchKernelGGL((zzt_dense_bf16_v9<true, false>), g9, dim3(NTH9), 0, s, a);
-    else hipLaunchKernelGGL((zzt_dense_bf16_v9<false, false>), g9, dim3(NTH9), 0, s, a);
-  } else if (dtype == SND_BF16 && dp <= 64) {         // v4 (default, d <= 64)
-    // variant >= 256: the measurement build (phase skips / stamps, variant >> 8)
-    if (a.variant >= 256) {
-      if (dp == 32) hipLaunchKernelGGL((zzt_dense_bf16_v4<32, true>), grid, dim3(NTH2), 0, s, a);
-      else hipLaunchKernelGGL((zzt_dense_bf16_v4<64, true>), grid, dim3(NTH2), 0, s, a);
-    } else {
-      if (dp == 32) hipLaunchKernelGGL((zzt_dense_bf16_v4<32, false>), grid, dim3(NTH2), 0, s, a);
-      else hipLaunchKernelGGL((zzt_dense_bf16_v4<64, false>), grid, dim3(NTH2), 0, s, a);
-    }
-  } else if (dtype == SND_BF16) {                     // v7 (d = 128)
-    if (a.variant >= 256) hipLaunchKernelGGL((zzt_dense_bf16_v7<true>), grid, dim3(NTH2), 0, s, a);
-    else hipLaunchKernelGGL((zzt_dense_bf16_v7<false>), grid, dim3(NTH2), 0, s, a);
-  } else {
+  if (dtype != SND_BF16) {                            // f32 parity mode
     const size_t shm = 2 * 2 * (size_t)TJ * dp * sizeof(float);
     if (dp == 32) hipLaunchKernelGGL((zzt_dense_f32<32>), grid, dim3(NTH), shm, s, a);
     else if (dp == 64) hipLaunchKernelGGL((zzt_dense_f32<64>), grid, dim3(NTH), shm, s, a);
     else hipLaunchKernelGGL((zzt_dense_f32<128>), grid, dim3(NTH), shm, s, a);
+  } else if (a.variant == 1) {                        // v1
+    if (dp == 32) hipLaunchKernelGGL((zzt_dense_bf16<32>), grid, dim3(NTH), 0, s, a);
+    else if (dp == 64) hipLaunchKernelGGL((zzt_dense_bf16<64>), grid, dim3(NTH), 0, s, a);
+    else hipLaunchKernelGGL((zzt_dense_bf16<128>), grid, dim3(NTH), 0, s, a);
+  } else if (dp == 32) {                              // v4; meas: phase skips / stamps, variant >> 8
+    if (meas) hipLaunchKernelGGL((zzt_dense_bf16_v4<32, true>), grid, dim3(NTH2), 0, s, a);
+    else hipLaunchKernelGGL((zzt_dense_bf16_v4<32, false>), grid, dim3(NTH2), 0, s, a);
+  } else if (dp == 64) {                              // v9: two 64-row workgroups per row block
+    const dim3 g9(grid.x * 2);
+    if (meas) hipLaunchKernelGGL((zzt_dense_bf16_v9<true>), g9, dim3(NTH9), 0, s, a);
+    else hipLaunchKernelGGL((zzt_dense_bf16_v9<false>), g9, dim3(NTH9), 0, s, a);
+  } else {                                            // v7 (d = 128)
+    if (meas) hipLaunchKernelGGL((zzt_dense_bf16_v7<true>), grid, dim3(NTH2), 0, s, a);
+    else hipLaunchKernelGGL((zzt_dense_bf16_v7<false>), grid, dim3(NTH2), 0, s, a);
   }
   SND_LAUNCH_CHECK("zzt_dense");
   if (ts > 1 && !defer_split) {

@@ -10,13 +10,12 @@ struct ZztArgs {
   float* dJd;            // [B*n][d]  sum_{j != i} sigmoid(L_ij) z_j
   double* part;          // [blocks][2] = {sum softplus over valid pairs, #{L > 0}}
   const float* colpart;  // [B][npad/64][DP] column sums of jrow (bf16 values), per 64 rows
-  int variant;           // bf16 kernel: 0 = default (v4 for d <= 64, v7 for d = 128), 1 = v1
-                         // (the bench's previous variant); >= 256 the measurement build of the
-                         // default (phase-skip / stamp bits variant >> 8, tools/zzt_stamps.py);
-                         // d = 64 (v9): variant & 255 = 9 .. 12 names one of its tile loops
-                         // (9 round 5's, 10 -z_i in registers, 11 + DMA two tiles ahead,
-                         // 12 + two-tile stages), column splits as the default
-  float* dJd_extra;      // v3 column splits 1.. (zzt_tsplit > 1): [(tsplit-1)][B*n][d] scratch
+  int variant;           // 0 = the default kernel (bf16: v4 at dp = 32, v9 at dp = 64, v7 at
+                         // dp = 128; f32: zzt_dense_f32); 1 = v1 (bf16; the bench's previous
+                         // variant); 256 * bits = the measurement build of the bf16 default
+                         // (phase-skip / stamp bits variant >> 8, tools/zzt_stamps.py).
+                         // launch_zzt_dense rejects every other value (SND_ERR_ARG)
+  float* dJd_extra;      // column splits 1.. (zzt_tsplit > 1): [(tsplit-1)][B*n][d] scratch
   int rb0 = 0;           // first 128-row block of the launch (row-sharded zz^T, snd_zzt_ce_rows)
   int nrb = 0;           // row blocks of the launch; 0 = every row block
   int tsplit = 0;        // column splits of the default bf16 kernel; 0 = zzt_tsplit's choice

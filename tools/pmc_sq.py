@@ -12,7 +12,7 @@ import sys
 
 def main():
     d, k = sys.argv[1], sys.argv[2]
-    sub = {"zzt_dense": "zzt_dense_bf16", "zzt_dense_v3": "zzt_dense_bf16_v3"}.get(k, k)
+    sub = {"zzt_dense": "zzt_dense_bf16"}.get(k, k)
     cnt = {}
     for path in sorted(glob.glob(os.path.join(d, "p*", "**", "*counter_collection.csv"), recursive=True)):
         last = {}
