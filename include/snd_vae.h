@@ -208,7 +208,9 @@ int snd_reparam_kl(const float* ms, int ldms, int rows, int latent,
  * Outputs (device): stats[0] = sum CE over all B*N*N pairs (double),
  *   stats[1] = number of pairs with argmax == A (as double),
  *   dz [B*N, d] = d(sum CE)/dz (unscaled; divide by B*N*N for the mean).
- * workspace: snd_zzt_ce_workspace() bytes. */
+ * workspace: snd_zzt_ce_workspace() bytes.  z, dz and the workspace must be 16-byte
+ * aligned (the kernels move them as 16-byte vectors; a row is at least 64 bytes);
+ * SND_ERR_ARG otherwise, before anything is launched. */
 size_t snd_zzt_ce_workspace(int n_graphs, int n, int d, int dtype);
 int snd_zzt_ce(const float* z, int n_graphs, int n, int d,
                const int* rowptr, const int* colidx, float pos_weight,
@@ -225,7 +227,8 @@ int snd_zzt_ce(const float* z, int n_graphs, int n, int d,
  *   dz [row1 - row0, d] = d(sum CE over ALL pairs)/dz for the range's rows -- L is
  *   symmetric, so a rank's rows need no reduction across ranks.
  * row0 % 128 == 0 and (row1 % 128 == 0 or row1 == n).  Summing stats over a
- * partition of [0, n) gives snd_zzt_ce's stats for the graph. */
+ * partition of [0, n) gives snd_zzt_ce's stats for the graph.  z, dz and the workspace
+ * must be 16-byte aligned, as for snd_zzt_ce. */
 size_t snd_zzt_ce_rows_workspace(int n, int d, int row0, int row1, int dtype);
 int snd_zzt_ce_rows(const float* z, int n, int d, int row0, int row1,
                     const int* rowptr, const int* colidx, float pos_weight, float norm,

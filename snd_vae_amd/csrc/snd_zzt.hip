@@ -1604,6 +1604,10 @@ extern "C" int snd_zzt_ce(const float* z, int n_graphs, int n, int d, const int*
   SND_CHECK_ARG(dtype == SND_F32 || dtype == SND_BF16, "snd_zzt_ce: bad dtype");
   const size_t need = snd_zzt_ce_workspace(n_graphs, n, d, dtype);
   SND_CHECK_ARG(ws && ws_bytes >= need, "snd_zzt_ce: workspace %zu < %zu", ws_bytes, need);
+  // edge_kernel reads z as float4, the dense kernels store float4 rows of dJd, the staging
+  // images are read as 16-byte vectors
+  SND_CHECK_ARG((((uintptr_t)z | (uintptr_t)dz | (uintptr_t)ws) & 15) == 0,
+                "snd_zzt_ce: z, dz and the workspace must be 16-byte aligned");
   SND_TRY(zzt_init_attributes());
   hipStream_t s = (hipStream_t)stream;
   char* p = (char*)ws;
@@ -1672,6 +1676,10 @@ extern "C" int snd_zzt_ce_rows(const float* z, int n, int d, int row0, int row1,
   size_t off[6], need;
   zrows_layout(n, d, row0, row1, dtype, off, &need);
   SND_CHECK_ARG(ws && ws_bytes >= need, "snd_zzt_ce_rows: workspace %zu < %zu", ws_bytes, need);
+  // edge_kernel reads z as float4, the dense kernels store float4 rows of dJd, the staging
+  // images are read as 16-byte vectors
+  SND_CHECK_ARG((((uintptr_t)z | (uintptr_t)dz | (uintptr_t)ws) & 15) == 0,
+                "snd_zzt_ce_rows: z, dz and the workspace must be 16-byte aligned");
   SND_TRY(zzt_init_attributes());
   hipStream_t s = (hipStream_t)stream;
   char* p = (char*)ws;

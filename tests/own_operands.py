@@ -163,6 +163,44 @@ def zzt_dp(d):
     return 32 if d <= 32 else (64 if d <= 64 else 128)
 
 
+def djd_graph(Jg, Vg, kinv, d, T, sr, round_s=True, r0=0, r1=None, diag_summed=False):
+    """One graph's dJd link (the dense zz^T kernels, snd_zzt.hip), rows [r0, r1): (ref, mag,
+    extra).  Jg [n, d] is the K role as stored (log2 units), Vg the V role as stored, kinv the
+    factor applied to the sum.  x_ij = J_i . J_j (fp32 MFMA), s_ij = 1 / (1 + 2^-x_ij),
+    dJd_i = kinv sum_{j != i} s_ij V_j.  s is within ds of the float64 value (fp32
+    accumulation of x, 1e-6 for exp2 / rcp).  ``round_s`` (the bf16 kernels): s is rounded to
+    bf16 (``sr``) before the second MFMA; where a rounding boundary lies within ds the term
+    may differ by one bf16 ulp of s, and those terms' |V_j| ulp(s) are the extra.  Otherwise
+    (the f32 kernels) the extra is ds |V| itself.  ``diag_summed``: the kernel adds s_ii V_i
+    with the tile and subtracts it afterwards (v4 / v7 / v9: no mask in the tile loop), so the
+    fp32 sum holds that term twice: 2 |s_ii V_i| joins mag (it matters where n is small)."""
+    f64 = np.float64
+    r1 = Jg.shape[0] if r1 is None else r1
+    idx = np.arange(r1 - r0)
+    x = Jg[r0:r1] @ Jg.T
+    sg = 1.0 / (1.0 + np.exp2(-x))
+    sb = T(sr(sg)) if round_s else T(sg)
+    sii = sb[idx, r0 + idx].copy()
+    sb[idx, r0 + idx] = 0.0
+    ref = (sb @ Vg) * kinv
+    mag = (sb @ np.abs(Vg)) * kinv
+    if diag_summed:
+        mag = mag + 2 * sii[:, None] * np.abs(Vg[r0:r1]) * kinv
+    s64 = np.asarray(sg, f64)
+    aJ = np.abs(Jg).astype(f64)
+    dx = (d + 4) * U23 * (aJ[r0:r1] @ aJ.T)
+    ds = s64 * (1 - s64) * LN2 * dx + 2 * TRANS * s64
+    if round_s:
+        ulp = np.exp2(np.floor(np.log2(np.maximum(s64, 1e-300))) - 7)
+        fr = s64 / ulp
+        w = (np.abs(fr - np.floor(fr) - 0.5) * ulp <= ds) * ulp   # (the diagonal too: s_ii is
+        # evaluated twice, in the tile and in the per-row correction that subtracts it)
+    else:
+        w = ds
+        w[idx, r0 + idx] = 0.0                                    # masked, never evaluated
+    return ref, mag, (w @ np.abs(Vg).astype(f64)) * float(kinv)
+
+
 class Plan:
     """What the plan decided and the test asserted: the K tails (columns of the operand past
     the packed bf16 image, multiplied by the fp32 weight rows: rowconv_kernel's ``wtail``)
@@ -300,21 +338,8 @@ def step_links(b: Dict[str, np.ndarray], p, batch, cfg, plan: Plan, dt=np.float6
     refs, mags, exts = [], [], []
     for g in range(B):
         Jg = J[g * n:(g + 1) * n]
-        Vg = Jg if scaled else ZB[g * n:(g + 1) * n]
-        x = Jg @ Jg.T
-        sg = 1.0 / (1.0 + np.exp2(-x))
-        sb = T(sr(sg))
-        np.fill_diagonal(sb, 0.0)
-        refs.append((sb @ Vg) * kinv)
-        mags.append((sb @ ab(Vg)) * kinv)
-        s64 = np.asarray(sg, f64)
-        dx = (dj + 4) * U23 * (np.abs(Jg).astype(f64) @ np.abs(Jg).astype(f64).T)
-        ds = s64 * (1 - s64) * LN2 * dx + 2 * TRANS * s64
-        ulp = np.exp2(np.floor(np.log2(np.maximum(s64, 1e-300))) - 7)
-        fr = s64 / ulp
-        amb = np.abs(fr - np.floor(fr) - 0.5) * ulp <= ds   # (the diagonal too: s_ii is
-        # evaluated twice, in the tile and in the per-row correction that subtracts it)
-        exts.append(((amb * ulp) @ np.abs(Vg).astype(f64)) * float(kinv))
+        r, m, e = djd_graph(Jg, Jg if scaled else ZB[g * n:(g + 1) * n], kinv, dj, T, sr)
+        refs.append(r), mags.append(m), exts.append(e)
     yield "DJD", Link(np.concatenate(refs), np.concatenate(mags), n + 2, extra=np.concatenate(exts))
     DJD = T(b["DJD"])
 

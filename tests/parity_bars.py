@@ -96,6 +96,29 @@ class Bars:
 
 
 # ---------------------------------------------------------------- own-operand structure
+def own_structure_dense(jrow):
+    """The dense kernel's share of own_structure from the staged rows jrow [B, n, d] (float64,
+    log2 units): (sum of softplus(L_ij) over i != j, #{x_ij > 0, i != j}, #{|L_ij| < 1e-4})."""
+    B, n = jrow.shape[:2]
+    ce = 0.0
+    dense_pos = amb = 0
+    for b in range(B):
+        J = jrow[b]
+        for lo in range(0, n, 1024):
+            hi = min(n, lo + 1024)
+            x = J[lo:hi] @ J.T                          # = L log2(e), exact products
+            L = x * LN2
+            sp = np.maximum(L, 0.0) + np.log1p(np.exp(-np.abs(L)))
+            idx = np.arange(hi - lo)
+            sp[idx, lo + idx] = 0.0
+            ce += float(sp.sum())
+            off = np.ones(L.shape, bool)
+            off[idx, lo + idx] = False
+            dense_pos += int(((x > 0) & off).sum())
+            amb += int(((np.abs(L) < 1e-4) & off).sum())
+    return ce, dense_pos, amb
+
+
 def own_structure(model, batch, cfg):
     """The CE sum (optimizer.py:142-144 summed over pairs, norm = pos_weight = 1) and the
     accuracy count (main.py:334) from the step's own bf16 operands, in float64.
@@ -114,23 +137,8 @@ def own_structure(model, batch, cfg):
     assert not jrow[:, :, d:].any() and not jrow[:, n:, :].any(), "own_structure: staging pad not zero"
     jrow = jrow[:, :, :d]
     zb = model.buffer("ZB", torch.bfloat16)[:B * n * d].view(B * n, d).double().cpu().numpy()
-    ce = absum = 0.0
-    dense_pos = amb = 0
-    for b in range(B):
-        J = jrow[b, :n]
-        for lo in range(0, n, 1024):
-            hi = min(n, lo + 1024)
-            x = J[lo:hi] @ J.T                          # = L log2(e), exact products
-            L = x * LN2
-            sp = np.maximum(L, 0.0) + np.log1p(np.exp(-np.abs(L)))
-            idx = np.arange(hi - lo)
-            sp[idx, lo + idx] = 0.0
-            ce += float(sp.sum())
-            absum += float(sp.sum())
-            off = np.ones(L.shape, bool)
-            off[idx, lo + idx] = False
-            dense_pos += int(((x > 0) & off).sum())
-            amb += int(((np.abs(L) < 1e-4) & off).sum())
+    ce, dense_pos, amb = own_structure_dense(jrow[:, :n])
+    absum = ce
     rows = np.repeat(np.arange(B * n), np.diff(batch.rowptr))
     Le = np.einsum("ek,ek->e", zb[rows], zb[batch.colidx])
     ce += -float(Le.sum()) + B * n * SOFTPLUS_M1
