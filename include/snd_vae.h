@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 25
+#define SND_ABI_VERSION 26
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -325,6 +325,55 @@ int snd_graph_stats(const int* rowptr, const int* colidx, int n_graphs, int n,
                     const float* coords, int ldc, int sd, float len_scale,
                     int* deg, int* tri2, long long* hist, long long* totals,
                     int accumulate, void* workspace, size_t workspace_bytes,
+                    snd_stream_t stream);
+
+/* ---- path statistics of a CSR and coordinates (ABI 26; forward only) ------------
+ * Does a generated spatial network work as a network?  Component structure, shortest-path
+ * hop counts and the detour (route factor, circuity) of the network route over the straight
+ * line (Barthelemy, Spatial networks, Phys. Rep. 499 (2011); Latora & Marchiori 2001 for
+ * the efficiency that follows from the hop histogram): what the reference's
+ * generation_evaluation / reconstruct_evaluation (main.py:423,467) are given the graphs
+ * and coordinates for.  B graphs x N nodes from the block-diagonal CSR of this header's
+ * preamble (what snd_zzt_edges writes), without a host round trip.  1 <= N <= 16384.
+ *   Edge rule (snd_graph_stats'): N(i) = the columns of row i inside i's graph block, i
+ *   itself left out; out-of-block entries and self loops are ignored, colidx in any order.
+ *   Duplicate entries are legal and change nothing (every operation below is idempotent).
+ *   Arcs are followed row -> column: the undirected graph on a symmetric CSR; on an
+ *   asymmetric one the formula is the definition.  colidx holds nnz_cap >= rowptr[B*N]
+ *   entries (NULL only with nnz_cap = 0).
+ * Sources of a graph: its local nodes 0, src_step, 2 src_step, ... (src_step >= 1);
+ * n_src = ceil(N / src_step).  Outputs (comp, hops_out and route_out may each be NULL):
+ *   comp [B*N] int32: the smallest local node id of the node's WEAKLY connected component
+ *             (arcs used both ways).
+ *   hops_out [B*n_src, N] int32: BFS arc count from each source; -1 where unreachable, 0
+ *             at the source.
+ *   route_out [B*n_src, N] fp32 (needs coords): the shortest route length, the least fixed
+ *             point in fp32 of d[s] = 0, d[v] = min_u fl(d[u] + len(u, v)), len the edge
+ *             length ||coords[u, :sd] - coords[v, :sd]||_2 formed once per CSR entry in fp32
+ *             (coords [B*N, ldc] fp32, 1 <= sd <= 3, ldc >= sd); +inf where unreachable.
+ *             fl(. + w) is monotone and w >= 0, so the fixed point is unique: it is what a
+ *             float32 Dijkstra returns, whatever the order of relaxations.
+ *   hist [B, 2, 256] int64:
+ *     hist[b][0][min(hops, 255)] += 1   per ordered pair (source s, t != s, reachable)
+ *     hist[b][1][min(max(floor((route / e - 1) detour_scale), 0), 255)] += 1   per such pair
+ *             with Euclidean distance e > 0, both distances fp32.  Left at zero when
+ *             coords == NULL; sd, ldc and detour_scale are ignored then.
+ *   totals [B, 6] int64 = {weak components, size of the largest, sources used, reachable
+ *             ordered pairs (s, t != s), sum of hops over them, largest hop count seen}.
+ * Every call clears hist and totals on the stream first (no accumulate mode: callers
+ * concatenate per batch).  Integer atomics only, no allocation, no host synchronisation:
+ * two runs are bitwise equal and a HIP-graph replay equals the eager call.  Non-finite
+ * coordinates: unspecified bins and routes, no fault, no store outside the outputs.
+ * SND_ERR_ARG before anything is launched: n_graphs < 1, n < 1, n > 16384, src_step < 1,
+ * nnz_cap < 0; route_out without coords; coords given with sd outside 1..3, ldc < sd or a
+ * NaN, non-positive or infinite detour_scale; NULL rowptr, hist or totals; a workspace
+ * below snd_graph_paths_workspace() bytes (one fp32 length per entry with coords, 0 and
+ * NULL accepted without).  Work: sources x arcs column ids, and that per relaxation sweep. */
+size_t snd_graph_paths_workspace(int n_graphs, int n, long long nnz_cap, int has_coords);
+int snd_graph_paths(const int* rowptr, const int* colidx, long long nnz_cap, int n_graphs, int n,
+                    const float* coords, int ldc, int sd, float detour_scale, int src_step,
+                    int* comp, int* hops_out, float* route_out, long long* hist,
+                    long long* totals, void* workspace, size_t workspace_bytes,
                     snd_stream_t stream);
 
 /* ---- a11: sigmoid head + MSE ----------------------------------------------

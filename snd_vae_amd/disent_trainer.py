@@ -244,8 +244,11 @@ class DisentTrainer:
         out["spatial_mse"] = spatial / (rows * self.cfg.spatial_dim)
         return out
 
+    PATH_DETOUR_SCALE = 64.0     # detour bins per unit of route / straight line - 1: 256 bins over [0, 4)
+
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
-                            inclusive: bool = True, seed: int = 0) -> dict:
+                            inclusive: bool = True, seed: int = 0, paths: bool = False,
+                            src_step: int = 1) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats) of the batch itself (its CSR and coordinates) and of a graph
         generated at its shape: mode "prior" decodes z ~ N(0, 1) (test_generation,
@@ -258,8 +261,12 @@ class DisentTrainer:
         Returns ``dataset.compare(generated)`` plus the two GraphStats under "dataset" and
         "generated", the threshold used and the generated graphs' (rowptr, colidx) per batch
         under "generated_csr".  Forward passes only; parameters, Adam state and the step
-        counter are not written."""
-        from .metrics import GraphStats
+        counter are not written.
+
+        paths=True adds "paths": the ``metrics.PathStats.compare`` (components, hop distances,
+        detour; every ``src_step``-th node a source, PATH_DETOUR_SCALE detour bins per unit) of
+        the same two sets of graphs, with the two PathStats under its "dataset" and "generated"."""
+        from .metrics import GraphStats, PathStats
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
@@ -268,19 +275,29 @@ class DisentTrainer:
                 raise ValueError("evaluate_generation: the dataset has no edge to choose a threshold by")
         B, N, sd = self.batch_size, self.cfg.n_nodes, self.cfg.spatial_dim
         max_len = math.sqrt(sd)
-        data, gen, csr = [], [], []
+        scale = self.PATH_DETOUR_SCALE
+        data, gen, csr, pdata, pgen = [], [], [], [], []
         for i, b in enumerate(self.batches):
             data.append(GraphStats(*layers.graph_stats(b.rowptr, b.colidx, B, N, b.spatial, max_len), N, max_len))
+            if paths:
+                pdata.append(PathStats(*layers.graph_paths(b.rowptr, b.colidx, B, N, b.spatial, scale, src_step),
+                                       N, scale, src_step))
             out = self.model.generate(b, z=mode, seed=seed + i, want_margin=True)
             m = out["margin"]
             dense = ((m >= threshold) if inclusive else (m > threshold)).float()   # the diagonal is ignored
             rowptr, colidx = layers.dense_to_csr(dense)
             coords = out["generated_spatial"].reshape(B * N, sd)
             gen.append(GraphStats(*layers.graph_stats(rowptr, colidx, B, N, coords, max_len), N, max_len))
+            if paths:
+                pgen.append(PathStats(*layers.graph_paths(rowptr, colidx, B, N, coords, scale, src_step),
+                                      N, scale, src_step))
             csr.append((rowptr, colidx))
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         out = data.compare(gen)
         out.update(dataset=data, generated=gen, threshold=threshold, generated_csr=csr)
+        if paths:
+            pdata, pgen = PathStats.concat(pdata), PathStats.concat(pgen)
+            out["paths"] = dict(pdata.compare(pgen), dataset=pdata, generated=pgen)
         return out
 
     def evaluate_disentanglement(self, n_bins: int = 20, factor_bins: Optional[int] = None) -> dict:

@@ -353,6 +353,80 @@ def graph_stats(rowptr, colidx, n_graphs, n, coords=None, max_len=None, hist=Non
     return (hist, totals, deg, tri2) if per_node else (hist, totals)
 
 
+def graph_paths(rowptr, colidx, n_graphs, n, coords=None, detour_scale=None, src_step=1, hist=None, totals=None,
+                per_node=False, per_source=False):
+    """Weak components, BFS hop distances and the detour of the shortest route over the
+    straight line of a block-diagonal CSR (snd_graph_paths), nothing read back.
+
+    rowptr / colidx: int32 device tensors as ``DeviceBatch`` holds and ``zzt_edges`` returns
+    them (entries outside a row's graph block and self loops are ignored, duplicates change
+    nothing; arcs are followed row -> column).  The sources of a graph are its local nodes 0,
+    src_step, 2 src_step, ...  coords: float32 device tensor [n_graphs * n, sd] with unit
+    column stride, 1 <= sd <= 3, or None (no routes, no detour histogram); ``detour_scale`` is
+    the number of bins per unit of route / straight line - 1 (the last of the 256 bins collects
+    larger detours) and is required with coords.
+    Returns (hist, totals): int64 [n_graphs, 2, 256] (hops, detour) and [n_graphs, 6] = {weak
+    components, size of the largest, sources, reachable ordered pairs, sum of hops, largest
+    hop count} (metrics.PathStats turns them into mean path length, efficiency, MMD ...); with
+    ``per_node`` also comp, int32 [n_graphs * n] (the smallest local id of the node's weak
+    component); with ``per_source`` also (hops, route): int32 and float32 [n_graphs * n_src, n],
+    -1 / inf where unreachable, route None without coords.  Given ``hist`` / ``totals`` are
+    cleared first.  No host synchronisation."""
+    if n_graphs < 1 or n < 1:
+        raise ValueError(f"graph_paths: expected n_graphs >= 1 and n >= 1, got {n_graphs} and {n}")
+    if src_step < 1:
+        raise ValueError(f"graph_paths: expected src_step >= 1, got {src_step}")
+    rows = n_graphs * n
+    # colidx may be empty (a generated graph without an edge): it is never read then
+    for t, name, numel in ((rowptr, "rowptr", rows + 1), (colidx, "colidx", 0)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() >= numel):
+            raise ValueError(f"graph_paths {name}: expected a contiguous int32 device tensor of >= {numel} elements")
+    ldc = sd = 0
+    scale = 0.0
+    if coords is not None:
+        if not (coords.is_cuda and coords.dtype == torch.float32 and coords.dim() == 2
+                and coords.shape[0] == rows and 1 <= coords.shape[1] <= 3
+                and (coords.shape[1] == 1 or coords.stride(1) == 1)):
+            raise ValueError(f"graph_paths coords: expected a float32 device tensor [{rows}, 1..3] with unit "
+                             "column stride")
+        if detour_scale is None or not (0.0 < float(detour_scale) < float("inf")):
+            raise ValueError(f"graph_paths: coords need a finite detour_scale > 0, got {detour_scale!r}")
+        sd = coords.shape[1]
+        ldc = coords.stride(0) if rows > 1 else max(sd, coords.stride(0))
+        scale = float(detour_scale)
+    elif detour_scale is not None:
+        raise ValueError("graph_paths: detour_scale without coords")
+    if (hist is None) != (totals is None):
+        raise ValueError("graph_paths: pass both hist and totals or neither")
+    dev = rowptr.device
+    if hist is None:
+        hist = torch.empty(n_graphs, 2, 256, dtype=torch.int64, device=dev)
+        totals = torch.empty(n_graphs, 6, dtype=torch.int64, device=dev)
+    for t, name, shape in ((hist, "hist", (n_graphs, 2, 256)), (totals, "totals", (n_graphs, 6))):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int64 and tuple(t.shape) == shape):
+            raise ValueError(f"graph_paths {name}: expected a contiguous int64 device tensor {list(shape)}")
+    n_src = (n + src_step - 1) // src_step
+    comp = torch.empty(rows, dtype=torch.int32, device=dev) if per_node else None
+    hops = route = None
+    if per_source:
+        hops = torch.empty(n_graphs * n_src, n, dtype=torch.int32, device=dev)
+        if coords is not None:
+            route = torch.empty(n_graphs * n_src, n, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    cap = colidx.numel()
+    wsb = L.snd_graph_paths_workspace(n_graphs, n, cap, int(coords is not None))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+    _lib.check(L.snd_graph_paths(_P(rowptr), _P(colidx) if cap else 0, cap, n_graphs, n, _P(coords), ldc, sd, scale,
+                                 int(src_step), _P(comp), _P(hops), _P(route), _P(hist), _P(totals), _P(ws), wsb,
+                                 _lib.stream_ptr()), "snd_graph_paths")
+    out = (hist, totals)
+    if per_node:
+        out += (comp,)
+    if per_source:
+        out += (hops, route)
+    return out
+
+
 def latent_mi(z, factors, n_bins=20, factor_bins=None, want_joint=False):
     """Mutual information between every latent dimension and every generative factor
     (snd_latent_mi), from joint histograms counted on chip; nothing is read back.

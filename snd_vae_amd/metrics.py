@@ -16,6 +16,9 @@ clustering and edge-length histograms per graph from ``snd_graph_stats``, and th
 two-sample statistics (MMD with an EMD kernel, KL divergence) between a set of
 generated graphs and the data.
 
+``PathStats`` is its companion for the graph as a network: components, hop distances
+and the detour of the network route over the straight line, from ``snd_graph_paths``.
+
 ``LatentMI`` (at the end) is the disentanglement side (`main.py:424`): MIG, avgMI,
 modularity and the per-group share of each factor's information, from the
 latent-factor mutual-information matrix of ``snd_latent_mi``.
@@ -513,6 +516,281 @@ class GraphStats:
 
     def __repr__(self) -> str:
         return f"GraphStats(n_graphs={self.n_graphs}, n={self.n}, max_len={self.max_len})"
+
+
+# ---------------------------------------------------------------------------
+# Path statistics from the counters of ``snd_graph_paths``
+# ---------------------------------------------------------------------------
+PATH_KINDS = ("hops", "detour")
+
+
+def _emd_mmd(ha: np.ndarray, hb: np.ndarray, width: float, sigma: float) -> float:
+    """GraphStats.mmd's statistic on two stacks of histograms [Ga, 256], [Gb, 256]."""
+    ca = np.cumsum(_normalised(ha), axis=1)
+    cb = np.cumsum(_normalised(hb), axis=1)
+    if ca.shape[0] == 0 or cb.shape[0] == 0:
+        return NAN
+
+    def mean_k(x, y):
+        tot = 0.0
+        step = max(1, (1 << 22) // (y.shape[0] * GS_BINS))
+        for i in range(0, x.shape[0], step):
+            d = np.abs(x[i:i + step, None, :] - y[None, :, :]).sum(axis=2) * width
+            tot += float(np.exp(-(d * d) / (2.0 * sigma * sigma)).sum())
+        return tot / (x.shape[0] * y.shape[0])
+
+    return mean_k(ca, ca) + mean_k(cb, cb) - 2.0 * mean_k(ca, cb)
+
+
+class PathStats:
+    """hist [G, 2, 256] and totals [G, 6] of a set of G graphs of n nodes each
+    (``layers.graph_paths`` / ``snd_graph_paths``): per graph the histogram of the hop count
+    of every reachable ordered pair (source, target != source) (bin = min(hops, 255)) and of
+    its detour route / straight line - 1 (256 bins of width 1 / detour_scale, the last one
+    collecting larger detours), and totals = {weak components, size of the largest, sources
+    used, reachable ordered pairs, sum of hops, largest hop count}.
+
+    Does a generated spatial network work as a network: does it hold together, is it as
+    wide as the data, does it connect nearby points without a long way round?  (Barthelemy,
+    Spatial networks, Phys. Rep. 499 (2011), sections 2.2.2-2.2.3: shortest paths, route
+    factor / detour index; the graphs and coordinates are what the reference hands to
+    ``generation_evaluation``, `main.py:467`.)  Same storage idiom as GraphStats: NumPy
+    arrays or two int64 torch tensors, device tensors read back once, on first use;
+    histograms stay per graph for the two-sample statistics.  ``detour_scale`` None: no
+    coordinates were given, the detour row is zero.  ``src_step`` > 1: the pairs are those of
+    every src_step-th node as source, a sample of the graph's pairs.
+    """
+
+    def __init__(self, hist, totals, n: int, detour_scale=None, src_step: int = 1):
+        self._dev = None
+        self._np = None
+        self.n = int(n)
+        self.src_step = int(src_step)
+        self.detour_scale = None if detour_scale is None else float(detour_scale)
+        if self.n < 1 or self.src_step < 1:
+            raise ValueError("PathStats: n and src_step must be >= 1")
+        if self.detour_scale is not None and not (0.0 < self.detour_scale < math.inf):
+            raise ValueError("PathStats: detour_scale must be finite and > 0")
+        if _is_tensor(hist):
+            if (hist.dim() != 3 or tuple(hist.shape[1:]) != (2, GS_BINS)
+                    or tuple(totals.shape) != (hist.shape[0], 6)):
+                raise ValueError("PathStats: expected hist [G, 2, 256] and totals [G, 6]")
+            self._dev = (hist, totals)
+        else:
+            h = np.asarray(hist, dtype=np.int64)
+            t = np.asarray(totals, dtype=np.int64)
+            if h.ndim == 2:
+                h, t = h[None], t.reshape(1, -1)
+            if h.ndim != 3 or h.shape[1:] != (2, GS_BINS) or t.shape != (h.shape[0], 6):
+                raise ValueError("PathStats: expected hist [G, 2, 256] and totals [G, 6]")
+            self._np = (h, t)
+
+    # ---- storage
+    @property
+    def tensors(self):
+        """The (hist, totals) torch tensors this object was built on, or None."""
+        return self._dev
+
+    def invalidate(self) -> None:
+        """Forget the host copy: the device tensors were written since it was read."""
+        if self._dev is not None:
+            self._np = None
+
+    def _arrays(self) -> Tuple[np.ndarray, np.ndarray]:
+        if self._np is None:
+            import torch
+            h, t = self._dev
+            both = torch.cat([h.reshape(-1), t.reshape(-1)]).cpu().numpy()     # one read-back
+            k = h.numel()
+            self._np = (both[:k].reshape(tuple(h.shape)), both[k:].reshape(tuple(t.shape)))
+        return self._np
+
+    @property
+    def hist(self) -> np.ndarray:
+        return self._arrays()[0]
+
+    @property
+    def totals(self) -> np.ndarray:
+        return self._arrays()[1]
+
+    @property
+    def n_graphs(self) -> int:
+        return int((self._dev[0] if self._np is None else self._np[0]).shape[0])
+
+    def _same_binning(self, other) -> bool:
+        return (self.n == other.n and self.detour_scale == other.detour_scale
+                and self.src_step == other.src_step)
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, PathStats) and self._same_binning(other)
+                and np.array_equal(self.hist, other.hist) and np.array_equal(self.totals, other.totals))
+
+    __hash__ = None
+
+    @classmethod
+    def concat(cls, parts) -> "PathStats":
+        """The graphs of several PathStats (batches of one dataset) as one set, in order."""
+        parts = list(parts)
+        if not parts or not all(isinstance(p, PathStats) for p in parts):
+            raise ValueError("PathStats.concat: expected a non-empty list of PathStats")
+        if any(not p._same_binning(parts[0]) for p in parts):
+            raise ValueError("PathStats.concat: the parts differ in n, detour_scale or src_step")
+        return cls(np.concatenate([p.hist for p in parts]), np.concatenate([p.totals for p in parts]),
+                   parts[0].n, parts[0].detour_scale, parts[0].src_step)
+
+    def all_gather(self, process_group=None) -> "PathStats":
+        """Every rank's graphs as one set, in rank order (data parallel; each rank holds the
+        same number of graphs), as a new PathStats: the same on every rank."""
+        import torch
+        import torch.distributed as dist
+        dev = self._dev[0].device if self._dev is not None else torch.device("cpu")
+        if dev.type == "cpu" and dist.get_backend(process_group) == "nccl":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self._dev is not None and self._dev[0].device == dev:
+            h, t = self._dev
+        else:
+            h = torch.from_numpy(self.hist.copy()).to(dev)
+            t = torch.from_numpy(self.totals.copy()).to(dev)
+        flat = torch.cat([h.reshape(-1), t.reshape(-1)])
+        world = dist.get_world_size(process_group)
+        out = [torch.empty_like(flat) for _ in range(world)]
+        dist.all_gather(out, flat, group=process_group)
+        k = h.numel()
+        hs = torch.cat([o[:k].reshape(h.shape) for o in out])
+        ts = torch.cat([o[k:].reshape(t.shape) for o in out])
+        return PathStats(hs, ts, self.n, self.detour_scale, self.src_step)
+
+    # ---- bins
+    def _kind(self, kind: str):
+        """(row of hist, bin width in the statistic's own units, default sigma)."""
+        if kind == "hops":
+            return 0, 1.0, 1.0
+        if kind == "detour":
+            if self.detour_scale is None:
+                raise ValueError("PathStats: no detours were binned (detour_scale is None)")
+            return 1, 1.0 / self.detour_scale, 0.1
+        raise ValueError(f"PathStats: kind must be one of {PATH_KINDS}, got {kind!r}")
+
+    # ---- scalar properties
+    def per_graph(self) -> dict:
+        """{property: float64 array [G]}:
+
+        * n_components = totals[0], the weakly connected components; connected = 1.0 where
+          that is 1; lcc_fraction = totals[1] / n, the share of the nodes in the largest one.
+        * mean_hops = totals[4] / totals[3]: the average shortest-path length <l> over the
+          reachable ordered pairs (Barthelemy 2011, eq. 21, restricted to reachable pairs;
+          networkx.average_shortest_path_length on a connected graph), exact; nan without a
+          pair.
+        * diameter = totals[5]: the largest hop count over the reachable pairs (the diameter
+          of a connected graph when every node is a source).
+        * global_efficiency = sum_h hist[0][h] / h / (sources (n - 1)): the mean of 1 / d(s, t)
+          over ordered pairs, unreachable pairs counting 0 (Latora & Marchiori, Phys. Rev.
+          Lett. 87 (2001) 198701, eq. 1; networkx.global_efficiency).  Exact while no pair
+          is past 254 hops: bin 255 collects them and enters as 1 / 255.  nan for n = 1.
+        * mean_detour = sum_b hist[1][b] (b + 1/2) / detour_scale / sum_b hist[1][b]: the mean
+          of route / straight line - 1 (the route factor or detour index minus one,
+          Barthelemy 2011, eq. 28) from the bin centres; nan without coordinates or pairs.
+        """
+        h, t = self.hist.astype(np.float64), self.totals.astype(np.float64)
+        out = {"n_components": t[:, 0], "connected": (t[:, 0] == 1).astype(np.float64),
+               "lcc_fraction": t[:, 1] / float(self.n), "diameter": t[:, 5]}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["mean_hops"] = np.where(t[:, 3] > 0, t[:, 4] / np.where(t[:, 3] > 0, t[:, 3], 1.0), NAN)
+            inv = np.r_[0.0, 1.0 / np.arange(1, GS_BINS, dtype=np.float64)]
+            den = t[:, 2] * (self.n - 1.0)
+            out["global_efficiency"] = np.where(den > 0, (h[:, 0, :] * inv).sum(axis=1) / np.where(den > 0, den, 1.0),
+                                                NAN)
+            if self.detour_scale is None:
+                out["mean_detour"] = np.full(h.shape[0], NAN)
+            else:
+                centres = (np.arange(GS_BINS, dtype=np.float64) + 0.5) / self.detour_scale
+                cnt = h[:, 1, :].sum(axis=1)
+                out["mean_detour"] = np.where(cnt > 0, (h[:, 1, :] * centres).sum(axis=1)
+                                              / np.where(cnt > 0, cnt, 1.0), NAN)
+        return out
+
+    def summary(self) -> dict:
+        """The set as a whole, as floats: n_components and lcc_fraction are means over the
+        graphs, connected the share of graphs with one component, diameter the maximum;
+        mean_hops, global_efficiency and mean_detour are those of the pooled counters (every
+        pair of every graph weighs the same).  nan where per_graph() has no value at all."""
+        if self.n_graphs == 0:
+            return {k: NAN for k in ("n_components", "connected", "lcc_fraction", "diameter", "mean_hops",
+                                     "global_efficiency", "mean_detour")}
+        pg = self.per_graph()
+        pooled = PathStats(self.hist.sum(axis=0, keepdims=True), self.totals.sum(axis=0, keepdims=True), self.n,
+                           self.detour_scale, self.src_step).per_graph()
+        return {"n_components": float(pg["n_components"].mean()), "connected": float(pg["connected"].mean()),
+                "lcc_fraction": float(pg["lcc_fraction"].mean()), "diameter": float(pg["diameter"].max()),
+                "mean_hops": float(pooled["mean_hops"][0]),
+                "global_efficiency": float(pooled["global_efficiency"][0]),
+                "mean_detour": float(pooled["mean_detour"][0])}
+
+    connected = property(lambda self: self.summary()["connected"])
+    mean_hops = property(lambda self: self.summary()["mean_hops"])
+    diameter = property(lambda self: self.summary()["diameter"])
+    global_efficiency = property(lambda self: self.summary()["global_efficiency"])
+    mean_detour = property(lambda self: self.summary()["mean_detour"])
+
+    # ---- two-sample statistics
+    def _check_other(self, other, kind):
+        if not isinstance(other, PathStats):
+            raise ValueError("PathStats: expected another PathStats")
+        row, width, sigma = self._kind(kind)
+        if kind == "detour" and other.detour_scale != self.detour_scale:
+            raise ValueError("PathStats: the two sides binned detours with different detour_scale")
+        return row, width, sigma
+
+    def mmd(self, other: "PathStats", kind: str, sigma=None) -> float:
+        """Biased (V-statistic) MMD^2 between two sets of graphs over their per-graph
+        normalised histograms of ``kind``, with GraphStats.mmd's kernel k = exp(-EMD^2 /
+        (2 sigma^2)), the EMD in the statistic's own units (hops; detour with bins of
+        1 / detour_scale).  Default sigma: 1.0 hop and 0.1 of detour.  A graph without a
+        pair enters as the zero histogram."""
+        row, width, s0 = self._check_other(other, kind)
+        sigma = s0 if sigma is None else float(sigma)
+        if not sigma > 0.0:
+            raise ValueError("PathStats.mmd: sigma must be > 0")
+        return _emd_mmd(self.hist[:, row, :], other.hist[:, row, :], width, sigma)
+
+    def pooled(self, kind: str) -> np.ndarray:
+        """The normalised histogram of ``kind`` over all graphs of the set."""
+        row, _, _ = self._kind(kind)
+        return _normalised(self.hist[:, row, :].sum(axis=0))
+
+    def kld(self, other: "PathStats", kind: str, eps: float = 1e-12) -> float:
+        """KL(self || other) of the pooled normalised histograms, each smoothed by eps per
+        bin and renormalised (scipy.stats.entropy(p + eps, q + eps)).  nan when either side
+        has no count."""
+        self._check_other(other, kind)
+        p, q = self.pooled(kind), other.pooled(kind)
+        if p.sum() == 0 or q.sum() == 0:
+            return NAN
+        p = (p + eps) / (p + eps).sum()
+        q = (q + eps) / (q + eps).sum()
+        return float(np.sum(p * np.log(p / q)))
+
+    def compare(self, other: "PathStats") -> dict:
+        """mmd_<kind>, kld_<kind> and emd_<kind> (the EMD of the pooled histograms) for
+        "hops" and (when both sides binned detours) "detour", plus both sides' summaries
+        under "self" and "other"."""
+        if not isinstance(other, PathStats):
+            raise ValueError("PathStats.compare: expected another PathStats")
+        out = {}
+        for kind in PATH_KINDS:
+            if kind == "detour" and (self.detour_scale is None or other.detour_scale is None):
+                continue
+            _, width, _ = self._check_other(other, kind)
+            out[f"mmd_{kind}"] = self.mmd(other, kind)
+            out[f"kld_{kind}"] = self.kld(other, kind)
+            out[f"emd_{kind}"] = emd(self.pooled(kind), other.pooled(kind), width)
+        out["self"] = self.summary()
+        out["other"] = other.summary()
+        return out
+
+    def __repr__(self) -> str:
+        return (f"PathStats(n_graphs={self.n_graphs}, n={self.n}, detour_scale={self.detour_scale}, "
+                f"src_step={self.src_step})")
 
 
 class LatentMI:

@@ -239,7 +239,7 @@ class SGCNModelVAE:
                  z: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                  seed: int = 0, step: int = 0, want_adj: bool = True, stream=None,
                  adj_format: str = "dense", threshold: float = 0.0, inclusive: bool = False,
-                 stats: bool = False) -> dict:
+                 stats: bool = False, paths: bool = False, src_step: int = 1) -> dict:
         """Forward-only decode (`main.py:358-469`, `model.py:163-169`).
 
         mode: "mean" (z = z_mean, reconstruction), "sample" (z = mu + eps e^s as
@@ -260,11 +260,17 @@ class SGCNModelVAE:
         stats=True (CSR format only): also "generated_stats", a metrics.GraphStats over
         device tensors from the generated CSR and generated_spatial (layers.graph_stats on
         the same stream; edge lengths over [0, sqrt(spatial_dim)], the unit box's diagonal).
+
+        paths=True (CSR format only): also "generated_paths", a metrics.PathStats over device
+        tensors from the same CSR and coordinates (layers.graph_paths; every ``src_step``-th
+        node a source, PATH_DETOUR_SCALE detour bins per unit).
         """
         if adj_format not in ("dense", "csr"):
             raise ValueError(f"adj_format must be 'dense' or 'csr', got {adj_format!r}")
         if stats and adj_format != "csr":
             raise ValueError("stats=True needs adj_format='csr': the statistics are taken from the CSR")
+        if paths and adj_format != "csr":
+            raise ValueError("paths=True needs adj_format='csr': the statistics are taken from the CSR")
         if adj_format == "dense" and (threshold != 0.0 or inclusive):
             raise ValueError("the dense generated_adj decides at L > 0 only: a threshold or "
                              "inclusive needs adj_format='csr'")
@@ -279,6 +285,8 @@ class SGCNModelVAE:
                 rowptr, colidx, nnz = layers.zzt_edges(self.joint_h, self.n_graphs, n, threshold, inclusive)
                 if stats:
                     gstats = self._graph_stats(rowptr, colidx, self.generated_spatial)
+                if paths:
+                    gpaths = self._graph_paths(rowptr, colidx, self.generated_spatial, src_step)
         else:
             self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
         out = {"generated_adj": adj,
@@ -289,6 +297,8 @@ class SGCNModelVAE:
             out.update(generated_rowptr=rowptr, generated_colidx=colidx, generated_nnz=nnz)
             if stats:
                 out["generated_stats"] = gstats
+            if paths:
+                out["generated_paths"] = gpaths
         if mode in ("mean", "sample"):
             out["z_mean"] = self.z_mean_sg.clone()
             out["z_std"] = self.z_std_sg.clone()
@@ -309,6 +319,24 @@ class SGCNModelVAE:
             raise ValueError("graph_stats: the batch does not match the plan's shape")
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             return self._graph_stats(batch.rowptr, batch.colidx, batch.spatial_truth)
+
+    PATH_DETOUR_SCALE = 64.0     # detour bins per unit of route / straight line - 1: 256 bins over [0, 4)
+
+    def _graph_paths(self, rowptr, colidx, coords, src_step):
+        """metrics.PathStats over fresh device counters (current stream, no read-back)."""
+        from . import layers
+        from .metrics import PathStats
+        scale = self.PATH_DETOUR_SCALE
+        hist, totals = layers.graph_paths(rowptr, colidx, self.n_graphs, self.cfg.n_nodes, coords, scale, src_step)
+        return PathStats(hist, totals, self.cfg.n_nodes, scale, src_step)
+
+    def graph_paths(self, batch: DeviceBatch, src_step: int = 1, stream=None):
+        """Path statistics (metrics.PathStats: components, hop distances, detour) of a
+        batch's own adjacency and ``spatial_truth``, every ``src_step``-th node a source."""
+        if batch.n_graphs != self.n_graphs or batch.n_nodes != self.cfg.n_nodes:
+            raise ValueError("graph_paths: the batch does not match the plan's shape")
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return self._graph_paths(batch.rowptr, batch.colidx, batch.spatial_truth, src_step)
 
     def _generate_launch(self, batch, mode, z, eps, seed, step, adj, stream):
         """snd_generate on the plan's workspace (argument checks of generate())."""

@@ -171,7 +171,8 @@ class Trainer:
         return out
 
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
-                            inclusive: bool = True, seed: int = 0) -> dict:
+                            inclusive: bool = True, seed: int = 0, paths: bool = False,
+                            src_step: int = 1) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats: degree, local clustering and edge length per graph) of the
         batch itself and of a graph generated at its shape: mode "prior" decodes z ~ N(0, 1)
@@ -183,25 +184,39 @@ class Trainer:
         both sides' pooled scalars) plus the two GraphStats under "dataset" and "generated"
         and the threshold used.  Forward passes only, outside the captured step graphs;
         parameters, Adam state and the step counter are not written.  Data parallel: every
-        rank's graphs are gathered, so all ranks return the same numbers."""
-        from .metrics import GraphStats
+        rank's graphs are gathered, so all ranks return the same numbers.
+
+        paths=True adds "paths": the ``metrics.PathStats.compare`` (components, hop distances,
+        detour; every ``src_step``-th node a source) of the same two sets of graphs, with the
+        two PathStats under its "dataset" and "generated"."""
+        from .metrics import GraphStats, PathStats
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
             threshold = self.evaluate(mode)["best_f1_threshold"]
             if threshold != threshold:                  # no positive anywhere: nothing to tune on
                 raise ValueError("evaluate_generation: the dataset has no edge to choose a threshold by")
-        data, gen = [], []
+        data, gen, pdata, pgen = [], [], [], []
         for i, b in enumerate(self.batches):
             data.append(self.model.graph_stats(b))
+            if paths:
+                pdata.append(self.model.graph_paths(b, src_step))
             out = self.model.generate(b if mode == "mean" else None, mode=mode, seed=seed, step=i,
-                                      adj_format="csr", threshold=threshold, inclusive=inclusive, stats=True)
+                                      adj_format="csr", threshold=threshold, inclusive=inclusive, stats=True,
+                                      paths=paths, src_step=src_step)
             gen.append(out["generated_stats"])
+            if paths:
+                pgen.append(out["generated_paths"])
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         if self.opt.distributed:
             data, gen = data.all_gather(self.opt.group), gen.all_gather(self.opt.group)
         out = data.compare(gen)
         out.update(dataset=data, generated=gen, threshold=threshold)
+        if paths:
+            pdata, pgen = PathStats.concat(pdata), PathStats.concat(pgen)
+            if self.opt.distributed:
+                pdata, pgen = pdata.all_gather(self.opt.group), pgen.all_gather(self.opt.group)
+            out["paths"] = dict(pdata.compare(pgen), dataset=pdata, generated=pgen)
         return out
 
     def save(self, path: str):
