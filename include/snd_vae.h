@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 26
+#define SND_ABI_VERSION 27
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -375,6 +375,47 @@ int snd_graph_paths(const int* rowptr, const int* colidx, long long nnz_cap, int
                     int* comp, int* hops_out, float* route_out, long long* hist,
                     long long* totals, void* workspace, size_t workspace_bytes,
                     snd_stream_t stream);
+
+/* ---- graphlet census of a CSR (ABI 27; forward only) ------------------------------
+ * The orbit descriptor of the graph-generation literature (GraphRNN, You et al. 2018, and
+ * its successors: degree, clustering and orbit counts) is, per graph, the mean over the nodes
+ * of the fifteen 2- to 4-node graphlet orbit counts.  Summed over a graph's nodes these
+ * follow exactly from nine induced subgraph counts, which this op leaves per graph, on the
+ * device, from the block-diagonal CSR of this header's preamble.  1 <= N <= 16384.
+ *   Entry rule (snd_graph_stats'): N(i) = the columns of row i inside i's graph block, i
+ *   itself left out; out-of-block entries and self loops are ignored, colidx in any order.
+ *   Duplicate entries: the first occurrence counts (the others are dropped on chip); the
+ *   contract leaves their effect unspecified, but no fault and no store outside the
+ *   outputs.  colidx holds nnz_cap >= rowptr[B*N] entries (NULL only with nnz_cap = 0).
+ *   The graph that is counted: the undirected simple graph G_b with {i, j} an edge iff
+ *   j in N(i) AND i in N(j).  On a symmetric CSR that is the graph itself; on an asymmetric
+ *   one this is the definition: a one-way arc (j in N(i), i not in N(j)) is no edge and is
+ *   counted in census[b][9].
+ * census [B, 10] int64: the numbers of INDUCED subgraphs of G_b
+ *   {0: E edges, 1: P2 open 2-paths, 2: T triangles, 3: P3 3-edge paths, 4: S3 claws
+ *    (3-stars), 5: C4 chordless 4-cycles, 6: TT tailed triangles (paws), 7: D diamonds,
+ *    8: K4 4-cliques} and 9: the one-way arcs.
+ * work [B] int64, always written: with l_i = rowptr[i + 1] - rowptr[i] the length of CSR row
+ *   i, and over the entries j of row i that count (in block, j != i; duplicates count here)
+ *   a_i = sum l_j and c_i = sum over those with j > i of l_j min(l_i, l_j),
+ *     work[b] = sum over the rows i of graph b of 9 l_i + 4 a_i + c_i,
+ *   an upper bound on the column ids the counting kernels read for graph b (the degrees of
+ *   G_b are at most the l_i; per triangle u < v < w the clique kernel reads one row w).  It
+ *   is computed in one pass of O(N + nnz) before any counting.  A graph with
+ *   work[b] > work_cap is NOT counted: its ten census entries are -1, every other graph of
+ *   the call is unaffected (4-clique counting is Theta(N^4) on a dense graph).
+ * Every call overwrites census and work (no accumulate mode).  Integer arithmetic and
+ * integer atomics only, no allocation, no host synchronisation: two runs are bitwise equal
+ * and a HIP-graph replay equals the eager call.
+ * SND_ERR_ARG before anything is launched, buffers untouched: n_graphs < 1; n < 1 or
+ * n > 16384; B N >= 2^31; nnz_cap < 0; work_cap < 0; NULL rowptr, census or work; NULL
+ * colidx with nnz_cap > 0; a workspace that is NULL, not 8-byte aligned or below
+ * snd_graph_motifs_workspace() bytes (the sums, one degree per row and the mutual-edge CSR:
+ * 80 B + 4 N B + 4 nnz_cap bytes, each part rounded up to 16 bytes; 0 for a shape the op rejects). */
+size_t snd_graph_motifs_workspace(int n_graphs, int n, long long nnz_cap);
+int snd_graph_motifs(const int* rowptr, const int* colidx, long long nnz_cap, int n_graphs, int n,
+                     long long work_cap, long long* census, long long* work, void* workspace,
+                     size_t workspace_bytes, snd_stream_t stream);
 
 /* ---- a11: sigmoid head + MSE ----------------------------------------------
  * Replaces tf.nn.sigmoid(linear(...)) (model_joint.py:121,144) and the

@@ -248,7 +248,7 @@ class DisentTrainer:
 
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
                             inclusive: bool = True, seed: int = 0, paths: bool = False,
-                            src_step: int = 1) -> dict:
+                            src_step: int = 1, motifs: bool = False) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats) of the batch itself (its CSR and coordinates) and of a graph
         generated at its shape: mode "prior" decodes z ~ N(0, 1) (test_generation,
@@ -265,8 +265,13 @@ class DisentTrainer:
 
         paths=True adds "paths": the ``metrics.PathStats.compare`` (components, hop distances,
         detour; every ``src_step``-th node a source, PATH_DETOUR_SCALE detour bins per unit) of
-        the same two sets of graphs, with the two PathStats under its "dataset" and "generated"."""
-        from .metrics import GraphStats, PathStats
+        the same two sets of graphs, with the two PathStats under its "dataset" and "generated".
+
+        motifs=True adds "motifs": the ``metrics.MotifStats.compare`` (orbit MMD, mean 4-node
+        graphlet frequencies) of the same two sets (``layers.graph_motifs``; a thresholded margin
+        may be asymmetric: its one-way arcs are no edges), with the two MotifStats under its
+        "dataset" and "generated"."""
+        from .metrics import GraphStats, MotifStats, PathStats
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
@@ -276,12 +281,14 @@ class DisentTrainer:
         B, N, sd = self.batch_size, self.cfg.n_nodes, self.cfg.spatial_dim
         max_len = math.sqrt(sd)
         scale = self.PATH_DETOUR_SCALE
-        data, gen, csr, pdata, pgen = [], [], [], [], []
+        data, gen, csr, pdata, pgen, mdata, mgen = [], [], [], [], [], [], []
         for i, b in enumerate(self.batches):
             data.append(GraphStats(*layers.graph_stats(b.rowptr, b.colidx, B, N, b.spatial, max_len), N, max_len))
             if paths:
                 pdata.append(PathStats(*layers.graph_paths(b.rowptr, b.colidx, B, N, b.spatial, scale, src_step),
                                        N, scale, src_step))
+            if motifs:
+                mdata.append(MotifStats(layers.graph_motifs(b.rowptr, b.colidx, B, N)[0], N))
             out = self.model.generate(b, z=mode, seed=seed + i, want_margin=True)
             m = out["margin"]
             dense = ((m >= threshold) if inclusive else (m > threshold)).float()   # the diagonal is ignored
@@ -291,6 +298,8 @@ class DisentTrainer:
             if paths:
                 pgen.append(PathStats(*layers.graph_paths(rowptr, colidx, B, N, coords, scale, src_step),
                                       N, scale, src_step))
+            if motifs:
+                mgen.append(MotifStats(layers.graph_motifs(rowptr, colidx, B, N)[0], N))
             csr.append((rowptr, colidx))
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         out = data.compare(gen)
@@ -298,6 +307,9 @@ class DisentTrainer:
         if paths:
             pdata, pgen = PathStats.concat(pdata), PathStats.concat(pgen)
             out["paths"] = dict(pdata.compare(pgen), dataset=pdata, generated=pgen)
+        if motifs:
+            mdata, mgen = MotifStats.concat(mdata), MotifStats.concat(mgen)
+            out["motifs"] = dict(mdata.compare(mgen), dataset=mdata, generated=mgen)
         return out
 
     def evaluate_disentanglement(self, n_bins: int = 20, factor_bins: Optional[int] = None) -> dict:

@@ -21,6 +21,10 @@ from . import _lib, ops
 from .model import DTYPES
 
 _P = _lib.ptr
+MOTIFS_MAX_N = 16384             # snd_graph_motifs: local ids are 16-bit on chip
+# Default work_cap of graph_motifs: the op ran 2.45e11 units of its work bound per second on K512
+# (tools/graph_motifs_timing.py), so a graph at this cap takes about a second.
+MOTIFS_WORK_CAP = 200_000_000_000
 
 
 def _dt(dtype):
@@ -425,6 +429,44 @@ def graph_paths(rowptr, colidx, n_graphs, n, coords=None, detour_scale=None, src
     if per_source:
         out += (hops, route)
     return out
+
+
+def graph_motifs(rowptr, colidx, n_graphs, n, work_cap=None):
+    """Graphlet census of a block-diagonal CSR (snd_graph_motifs), nothing read back.
+
+    rowptr / colidx: int32 device tensors as ``DeviceBatch`` holds and ``zzt_edges`` /
+    ``dense_to_csr`` return them (entries outside a row's graph block and self loops are
+    ignored).  The graph that is counted has {i, j} as an edge iff both arcs are present; a
+    one-way arc is no edge.  Returns (census, work): int64 device tensors [n_graphs, 10] =
+    {E, P2, T, P3, S3, C4, TT, D, K4 induced subgraph counts, one-way arcs} and [n_graphs], the
+    bound on the column ids the counting reads per graph (the header has the formula).  A graph
+    with work > ``work_cap`` (default MOTIFS_WORK_CAP) is not counted: its census row is -1.
+    ``metrics.MotifStats`` turns the census into orbit vectors and their MMD.  No host
+    synchronisation."""
+    if n_graphs < 1 or n < 1:
+        raise ValueError(f"graph_motifs: expected n_graphs >= 1 and n >= 1, got {n_graphs} and {n}")
+    if n > MOTIFS_MAX_N:
+        raise ValueError(f"graph_motifs: n = {n} > {MOTIFS_MAX_N}")
+    work_cap = MOTIFS_WORK_CAP if work_cap is None else int(work_cap)
+    if work_cap < 0:
+        raise ValueError(f"graph_motifs: expected work_cap >= 0, got {work_cap}")
+    rows = n_graphs * n
+    # colidx may be empty (a generated graph without an edge): it is never read then
+    for t, name, numel in ((rowptr, "rowptr", rows + 1), (colidx, "colidx", 0)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() >= numel):
+            raise ValueError(f"graph_motifs {name}: expected a contiguous int32 device tensor of >= {numel} elements")
+    dev = rowptr.device
+    census = torch.empty(n_graphs, 10, dtype=torch.int64, device=dev)
+    work = torch.empty(n_graphs, dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    cap = colidx.numel()
+    wsb = L.snd_graph_motifs_workspace(n_graphs, n, cap)
+    if wsb == 0:
+        raise _lib.SNDError(f"snd_graph_motifs_workspace: bad shape n_graphs={n_graphs} n={n}")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(L.snd_graph_motifs(_P(rowptr), _P(colidx) if cap else 0, cap, n_graphs, n, work_cap, _P(census),
+                                  _P(work), _P(ws), wsb, _lib.stream_ptr()), "snd_graph_motifs")
+    return census, work
 
 
 def latent_mi(z, factors, n_bins=20, factor_bins=None, want_joint=False):

@@ -239,7 +239,7 @@ class SGCNModelVAE:
                  z: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                  seed: int = 0, step: int = 0, want_adj: bool = True, stream=None,
                  adj_format: str = "dense", threshold: float = 0.0, inclusive: bool = False,
-                 stats: bool = False, paths: bool = False, src_step: int = 1) -> dict:
+                 stats: bool = False, paths: bool = False, src_step: int = 1, motifs: bool = False) -> dict:
         """Forward-only decode (`main.py:358-469`, `model.py:163-169`).
 
         mode: "mean" (z = z_mean, reconstruction), "sample" (z = mu + eps e^s as
@@ -264,6 +264,9 @@ class SGCNModelVAE:
         paths=True (CSR format only): also "generated_paths", a metrics.PathStats over device
         tensors from the same CSR and coordinates (layers.graph_paths; every ``src_step``-th
         node a source, PATH_DETOUR_SCALE detour bins per unit).
+
+        motifs=True (CSR format only): also "generated_motifs", a metrics.MotifStats over the
+        device census of the generated CSR (layers.graph_motifs at its default work_cap).
         """
         if adj_format not in ("dense", "csr"):
             raise ValueError(f"adj_format must be 'dense' or 'csr', got {adj_format!r}")
@@ -271,6 +274,8 @@ class SGCNModelVAE:
             raise ValueError("stats=True needs adj_format='csr': the statistics are taken from the CSR")
         if paths and adj_format != "csr":
             raise ValueError("paths=True needs adj_format='csr': the statistics are taken from the CSR")
+        if motifs and adj_format != "csr":
+            raise ValueError("motifs=True needs adj_format='csr': the census is taken from the CSR")
         if adj_format == "dense" and (threshold != 0.0 or inclusive):
             raise ValueError("the dense generated_adj decides at L > 0 only: a threshold or "
                              "inclusive needs adj_format='csr'")
@@ -287,6 +292,8 @@ class SGCNModelVAE:
                     gstats = self._graph_stats(rowptr, colidx, self.generated_spatial)
                 if paths:
                     gpaths = self._graph_paths(rowptr, colidx, self.generated_spatial, src_step)
+                if motifs:
+                    gmotifs = self._graph_motifs(rowptr, colidx)
         else:
             self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
         out = {"generated_adj": adj,
@@ -299,6 +306,8 @@ class SGCNModelVAE:
                 out["generated_stats"] = gstats
             if paths:
                 out["generated_paths"] = gpaths
+            if motifs:
+                out["generated_motifs"] = gmotifs
         if mode in ("mean", "sample"):
             out["z_mean"] = self.z_mean_sg.clone()
             out["z_std"] = self.z_std_sg.clone()
@@ -337,6 +346,21 @@ class SGCNModelVAE:
             raise ValueError("graph_paths: the batch does not match the plan's shape")
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             return self._graph_paths(batch.rowptr, batch.colidx, batch.spatial_truth, src_step)
+
+    def _graph_motifs(self, rowptr, colidx):
+        """metrics.MotifStats over a fresh device census (current stream, no read-back)."""
+        from . import layers
+        from .metrics import MotifStats
+        census, _ = layers.graph_motifs(rowptr, colidx, self.n_graphs, self.cfg.n_nodes)
+        return MotifStats(census, self.cfg.n_nodes)
+
+    def graph_motifs(self, batch: DeviceBatch, stream=None):
+        """Graphlet census (metrics.MotifStats: the nine induced 2- to 4-node subgraph counts
+        per graph, orbit vectors, MMD) of a batch's own adjacency."""
+        if batch.n_graphs != self.n_graphs or batch.n_nodes != self.cfg.n_nodes:
+            raise ValueError("graph_motifs: the batch does not match the plan's shape")
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return self._graph_motifs(batch.rowptr, batch.colidx)
 
     def _generate_launch(self, batch, mode, z, eps, seed, step, adj, stream):
         """snd_generate on the plan's workspace (argument checks of generate())."""

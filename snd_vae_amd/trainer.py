@@ -172,7 +172,7 @@ class Trainer:
 
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
                             inclusive: bool = True, seed: int = 0, paths: bool = False,
-                            src_step: int = 1) -> dict:
+                            src_step: int = 1, motifs: bool = False) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats: degree, local clustering and edge length per graph) of the
         batch itself and of a graph generated at its shape: mode "prior" decodes z ~ N(0, 1)
@@ -188,25 +188,33 @@ class Trainer:
 
         paths=True adds "paths": the ``metrics.PathStats.compare`` (components, hop distances,
         detour; every ``src_step``-th node a source) of the same two sets of graphs, with the
-        two PathStats under its "dataset" and "generated"."""
-        from .metrics import GraphStats, PathStats
+        two PathStats under its "dataset" and "generated".
+
+        motifs=True adds "motifs": the ``metrics.MotifStats.compare`` (orbit MMD, mean 4-node
+        graphlet frequencies) of the same two sets, with the two MotifStats under its
+        "dataset" and "generated"."""
+        from .metrics import GraphStats, MotifStats, PathStats
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
             threshold = self.evaluate(mode)["best_f1_threshold"]
             if threshold != threshold:                  # no positive anywhere: nothing to tune on
                 raise ValueError("evaluate_generation: the dataset has no edge to choose a threshold by")
-        data, gen, pdata, pgen = [], [], [], []
+        data, gen, pdata, pgen, mdata, mgen = [], [], [], [], [], []
         for i, b in enumerate(self.batches):
             data.append(self.model.graph_stats(b))
             if paths:
                 pdata.append(self.model.graph_paths(b, src_step))
+            if motifs:
+                mdata.append(self.model.graph_motifs(b))
             out = self.model.generate(b if mode == "mean" else None, mode=mode, seed=seed, step=i,
                                       adj_format="csr", threshold=threshold, inclusive=inclusive, stats=True,
-                                      paths=paths, src_step=src_step)
+                                      paths=paths, src_step=src_step, motifs=motifs)
             gen.append(out["generated_stats"])
             if paths:
                 pgen.append(out["generated_paths"])
+            if motifs:
+                mgen.append(out["generated_motifs"])
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         if self.opt.distributed:
             data, gen = data.all_gather(self.opt.group), gen.all_gather(self.opt.group)
@@ -217,6 +225,11 @@ class Trainer:
             if self.opt.distributed:
                 pdata, pgen = pdata.all_gather(self.opt.group), pgen.all_gather(self.opt.group)
             out["paths"] = dict(pdata.compare(pgen), dataset=pdata, generated=pgen)
+        if motifs:
+            mdata, mgen = MotifStats.concat(mdata), MotifStats.concat(mgen)
+            if self.opt.distributed:
+                mdata, mgen = mdata.all_gather(self.opt.group), mgen.all_gather(self.opt.group)
+            out["motifs"] = dict(mdata.compare(mgen), dataset=mdata, generated=mgen)
         return out
 
     def save(self, path: str):
