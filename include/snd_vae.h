@@ -137,7 +137,8 @@ int snd_csr_spmm_bf16_tiled(const int* rowptr, const int* colidx, int n_rows,
  *              to a multiple of 8 and to the largest degree (<= 32) of its
  *              wavefront group (8 consecutive rows of the listing below); the
  *              kernel reads 32 entries from every list start, so the array holds
- *              24 entries past the end of the last list
+ *              24 entries past the end of the last list, and 32 past the start
+ *              of a trailing empty list (a row of an all-empty group)
  *   rows[q]  = the row whose sums position q computes, and meta[q] its meta:
  *              inside each aligned 128-position block listed by degree,
  *              descending (a wave's 8 rows then share their neighbour count)

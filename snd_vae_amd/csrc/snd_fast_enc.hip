@@ -992,6 +992,12 @@ extern "C" int snd_csr_spmm_bf16_tiled(const int* rowptr, const int* colidx, int
                                        const int* row_order, snd_stream_t stream) {
   SND_CHECK_ARG(rowptr && (colidx || n_rows == 0) && h && out && n_rows >= 0 && tiles && tiles->tile_rows > 0,
                 "snd_csr_spmm_bf16_tiled: null operand or no tiles");
+  // restated from launch_spmm_bf16 (which accepts anything at n_rows = 0): its messages name no entry point
+  SND_CHECK_ARG(n_rows == 0 || tiles->tile_rows <= TRPG * TG, "snd_csr_spmm_bf16_tiled: tile_rows %d (<= %d)", tiles->tile_rows,
+                TRPG * TG);
+  SND_CHECK_ARG(n_rows == 0 || (width > 0 && width % 8 == 0 && width <= 128 && ldh % 8 == 0 && ldo % 8 == 0),
+                "snd_csr_spmm_bf16_tiled: 0 < width %% 8 <= 128, ldh and ldo %% 8 (width %d, ldh %d, ldo %d)", width,
+                ldh, ldo);
   SpmmBfArgs a{rowptr, colidx, n_rows, reinterpret_cast<const __bf16*>(h), ldh, width,
                SND_SPMM_PLAIN, reinterpret_cast<__bf16*>(out), ldo};
   a.xcd_nbg = 0;

@@ -404,9 +404,12 @@ def window_plan(batch: GraphBatch, order: np.ndarray, ring: int = 1096) -> Windo
     if start[-1] // 8 >= (1 << 25):
         raise ValueError("window_plan: slot lists exceed the 25-bit offset")
     nnz = int(deg.sum())
-    # + 24: the kernel DMAs 32 entries of every row's list (8 rows x 4 lanes x 16 B), so
-    # the last list (8 entries) is followed by 24 padding entries inside the array
-    slots = np.full(max(int(start[-1]), 8) + 24, ring, np.uint16)
+    # the kernel DMAs 32 entries from every row's list start (8 rows x 4 lanes x 16 B), so
+    # the array reaches 32 entries past the last start: 24 padding entries after a last
+    # list of 8, and 32 after trailing empty lists (the rows of an all-empty group), whose
+    # start is the array's end
+    last = int(start[:-1].max()) if R else 0
+    slots = np.full(max(int(start[-1]) + 24, last + 32), ring, np.uint16)
     beta = 0
     if nnz:
         excl = np.cumsum(deg) - deg               # exclusive prefix of degrees

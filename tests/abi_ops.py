@@ -40,7 +40,8 @@ F32, BF16 = 0, 1                      # SND_F32 / SND_BF16
 G = 64                                # guard elements (a multiple of 8: 16-byte aligned blocks)
 # dtype -> (array dtype, integer view, guard pattern); the float patterns are quiet NaNs
 PATTERN = {"f32": (np.float32, np.uint32, 0x7FC5A5A5), "bf16": (np.uint16, np.uint16, 0x7FC5),
-           "f64": (np.float64, np.uint64, 0x7FF8A5A5A5A5A5A5), "i32": (np.int32, np.uint32, 0x7FC5A5A5)}
+           "f64": (np.float64, np.uint64, 0x7FF8A5A5A5A5A5A5), "i32": (np.int32, np.uint32, 0x7FC5A5A5),
+           "u16": (np.uint16, np.uint16, 0xA5C5)}     # raw uint16 operands ("bf16" converts its data)
 
 
 def bf16_bits(a):
