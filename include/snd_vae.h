@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 27
+#define SND_ABI_VERSION 28
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -417,6 +417,55 @@ size_t snd_graph_motifs_workspace(int n_graphs, int n, long long nnz_cap);
 int snd_graph_motifs(const int* rowptr, const int* colidx, long long nnz_cap, int n_graphs, int n,
                      long long work_cap, long long* census, long long* work, void* workspace,
                      size_t workspace_bytes, snd_stream_t stream);
+
+/* ---- spectral density of a CSR (ABI 28; forward only) -----------------------------
+ * The fourth descriptor of the graph-generation literature (GRAN, Liao et al. 2019: degree,
+ * clustering, orbits and the spectrum of the normalised Laplacian), without an eigensolver:
+ * the Chebyshev moments of the spectral density by the kernel polynomial method (Weisse et
+ * al., Rev. Mod. Phys. 78, 2006), per graph, on the device, from the block-diagonal CSR of
+ * this header's preamble.  1 <= N <= 16384.
+ *   The graph (snd_graph_motifs'): N(i) = the columns of row i inside i's graph block, i
+ *   itself left out; out-of-block entries and self loops are ignored, colidx in any order;
+ *   {i, j} is an edge iff j in N(i) AND i in N(j); a one-way arc is no edge and is counted
+ *   in info[b][2].  Duplicate entries: every copy counts as an entry of its own; the
+ *   contract leaves their effect unspecified, but no fault and no store outside the
+ *   outputs.  colidx holds nnz_cap >= rowptr[B*N] entries (NULL only with nnz_cap = 0).
+ *   The operator: with d_i the degree in that graph, M = L - I, L = D^-1/2 (D - A) D^-1/2
+ *   and d^-1/2 := 0 for an isolated node (networkx's and scipy's convention: an isolated
+ *   node has eigenvalue 0 of L):
+ *     (M x)_i = - sum_{j in N(i), mutual} x_j / sqrt(d_i d_j)  if d_i > 0,  else -x_i.
+ *   The spectrum of M lies in [-1, 1].
+ * moments [B, n_moments] double, 2 <= n_moments <= 512:
+ *   n_probes = 0 (exact): moments[b][k] = tr T_k(M_b) = sum_i T_k(lambda_i - 1), T_k the
+ *     Chebyshev polynomial, computed with the N unit vectors as probes;
+ *   n_probes = R >= 1: (1 / R) sum_r v_r^T T_k(M_b) v_r with v_r[i] = +-1: -1 iff bit 0 of
+ *     the first output word of Philox4x32-10 with counter (i, r, b, 0x53504543) and key
+ *     (seed lo, seed hi) is set; i is the node's local index, b its graph's index in the
+ *     call (a Hutchinson estimate: the error of a raw moment is about sqrt(2 N / R)).
+ *   moments[b][0] = N exactly in both modes; in exact mode moments[b][1] = -isolated exactly.
+ * info [B, 4] int64: {edges, isolated nodes, one-way arcs, probes used (N in exact mode)}.
+ * Arithmetic: state, weights and sums in double.  With t_0 = v, t_1 = M t_0,
+ *   t_{s+1} = 2 M t_s - t_{s-1}:  mu_{2s+1} = 2 <t_{s+1}, t_s> - mu_1 and
+ *   mu_{2s+2} = 2 <t_{s+1}, t_{s+1}> - mu_0 (M is symmetric), so K moments take K / 2
+ *   applications of M.  Probes run in column blocks of 32; for N <= 64 a workgroup per graph
+ *   runs the whole recurrence in LDS in one launch per probe block, above that (or with
+ *   SND_SPECTRUM_FORCE_GLOBAL in flags; every other bit must be 0) one fused launch and
+ *   one fixed-order reduction per step.  No floating-point atomics: two runs are bitwise
+ *   equal and a HIP-graph replay equals the eager call; the launch count depends on N,
+ *   n_moments, n_probes and flags only.  No allocation, no host synchronisation.
+ * Every call overwrites moments and info.
+ * SND_ERR_ARG before anything is launched, buffers untouched: n_graphs < 1; n < 1 or
+ * n > 16384; B N >= 2^31; nnz_cap < 0; n_moments outside [2, 512]; n_probes < 0; unknown
+ * flag bits; NULL rowptr, moments or info; NULL colidx with nnz_cap > 0; a workspace that
+ * is NULL, not 8-byte aligned or below snd_graph_spectrum_workspace() bytes (32 B per
+ * graph, 8 B per entry, two state buffers of 256 B per row, 16 B per 8 rows of partial
+ * dots, 4 B per row, each part rounded up to 16 bytes; 0 for a shape the op rejects). */
+enum { SND_SPECTRUM_FORCE_GLOBAL = 1 };
+size_t snd_graph_spectrum_workspace(int n_graphs, int n, long long nnz_cap);
+int snd_graph_spectrum(const int* rowptr, const int* colidx, long long nnz_cap, int n_graphs, int n,
+                       int n_moments, int n_probes, unsigned long long seed, int flags,
+                       double* moments, long long* info, void* workspace, size_t workspace_bytes,
+                       snd_stream_t stream);
 
 /* ---- a11: sigmoid head + MSE ----------------------------------------------
  * Replaces tf.nn.sigmoid(linear(...)) (model_joint.py:121,144) and the

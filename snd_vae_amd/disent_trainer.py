@@ -248,7 +248,7 @@ class DisentTrainer:
 
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
                             inclusive: bool = True, seed: int = 0, paths: bool = False,
-                            src_step: int = 1, motifs: bool = False) -> dict:
+                            src_step: int = 1, motifs: bool = False, spectrum: bool = False) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats) of the batch itself (its CSR and coordinates) and of a graph
         generated at its shape: mode "prior" decodes z ~ N(0, 1) (test_generation,
@@ -270,8 +270,13 @@ class DisentTrainer:
         motifs=True adds "motifs": the ``metrics.MotifStats.compare`` (orbit MMD, mean 4-node
         graphlet frequencies) of the same two sets (``layers.graph_motifs``; a thresholded margin
         may be asymmetric: its one-way arcs are no edges), with the two MotifStats under its
-        "dataset" and "generated"."""
-        from .metrics import GraphStats, MotifStats, PathStats
+        "dataset" and "generated".
+
+        spectrum=True adds "spectrum": the ``metrics.SpectrumStats.compare`` (MMD and KL
+        divergence of the spectral densities of the normalised Laplacian;
+        ``layers.graph_spectrum`` at its defaults) of the same two sets, with the two
+        SpectrumStats under its "dataset" and "generated"."""
+        from .metrics import GraphStats, MotifStats, PathStats, SpectrumStats
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
@@ -281,7 +286,7 @@ class DisentTrainer:
         B, N, sd = self.batch_size, self.cfg.n_nodes, self.cfg.spatial_dim
         max_len = math.sqrt(sd)
         scale = self.PATH_DETOUR_SCALE
-        data, gen, csr, pdata, pgen, mdata, mgen = [], [], [], [], [], [], []
+        data, gen, csr, pdata, pgen, mdata, mgen, sdata, sgen = [], [], [], [], [], [], [], [], []
         for i, b in enumerate(self.batches):
             data.append(GraphStats(*layers.graph_stats(b.rowptr, b.colidx, B, N, b.spatial, max_len), N, max_len))
             if paths:
@@ -289,6 +294,8 @@ class DisentTrainer:
                                        N, scale, src_step))
             if motifs:
                 mdata.append(MotifStats(layers.graph_motifs(b.rowptr, b.colidx, B, N)[0], N))
+            if spectrum:
+                sdata.append(SpectrumStats(*layers.graph_spectrum(b.rowptr, b.colidx, B, N), N))
             out = self.model.generate(b, z=mode, seed=seed + i, want_margin=True)
             m = out["margin"]
             dense = ((m >= threshold) if inclusive else (m > threshold)).float()   # the diagonal is ignored
@@ -300,6 +307,8 @@ class DisentTrainer:
                                       N, scale, src_step))
             if motifs:
                 mgen.append(MotifStats(layers.graph_motifs(rowptr, colidx, B, N)[0], N))
+            if spectrum:
+                sgen.append(SpectrumStats(*layers.graph_spectrum(rowptr, colidx, B, N), N))
             csr.append((rowptr, colidx))
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         out = data.compare(gen)
@@ -310,6 +319,9 @@ class DisentTrainer:
         if motifs:
             mdata, mgen = MotifStats.concat(mdata), MotifStats.concat(mgen)
             out["motifs"] = dict(mdata.compare(mgen), dataset=mdata, generated=mgen)
+        if spectrum:
+            sdata, sgen = SpectrumStats.concat(sdata), SpectrumStats.concat(sgen)
+            out["spectrum"] = dict(sdata.compare(sgen), dataset=sdata, generated=sgen)
         return out
 
     def evaluate_disentanglement(self, n_bins: int = 20, factor_bins: Optional[int] = None) -> dict:

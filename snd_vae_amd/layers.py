@@ -25,6 +25,10 @@ MOTIFS_MAX_N = 16384             # snd_graph_motifs: local ids are 16-bit on chi
 # Default work_cap of graph_motifs: the op ran 2.45e11 units of its work bound per second on K512
 # (tools/graph_motifs_timing.py), so a graph at this cap takes about a second.
 MOTIFS_WORK_CAP = 200_000_000_000
+SPECTRUM_MAX_N = 16384           # snd_graph_spectrum
+SPECTRUM_MAX_MOMENTS = 512
+SPECTRUM_EXACT_MAX_N = 256       # graph_spectrum's default: exact traces up to here ...
+SPECTRUM_PROBES = 32             # ... and this many Rademacher probes above
 
 
 def _dt(dtype):
@@ -467,6 +471,52 @@ def graph_motifs(rowptr, colidx, n_graphs, n, work_cap=None):
     _lib.check(L.snd_graph_motifs(_P(rowptr), _P(colidx) if cap else 0, cap, n_graphs, n, work_cap, _P(census),
                                   _P(work), _P(ws), wsb, _lib.stream_ptr()), "snd_graph_motifs")
     return census, work
+
+
+def graph_spectrum(rowptr, colidx, n_graphs, n, n_moments=128, n_probes=None, seed=0, force_global=False):
+    """Chebyshev moments of the spectral density of the normalised Laplacian of every graph of
+    a block-diagonal CSR (snd_graph_spectrum), nothing read back.
+
+    rowptr / colidx: int32 device tensors as ``DeviceBatch`` holds and ``zzt_edges`` /
+    ``dense_to_csr`` return them; the graph is ``graph_motifs``' ({i, j} an edge iff both arcs
+    are present; out-of-block entries and self loops ignored).  ``n_probes=None``: exact traces
+    (0 probes: the n unit vectors) for n <= SPECTRUM_EXACT_MAX_N, SPECTRUM_PROBES Rademacher
+    probes above; ``seed`` keys their Philox stream.  ``force_global`` takes the per-step
+    kernels at n <= 64 too (the LDS path's counterpart in tests and timing).  Returns
+    (moments, info): float64 [n_graphs, n_moments] = tr T_k(L - I) and int64 [n_graphs, 4] =
+    {edges, isolated nodes, one-way arcs, probes used}.  ``metrics.SpectrumStats`` rebuilds the
+    eigenvalue histogram from them.  No host synchronisation."""
+    if n_graphs < 1 or n < 1:
+        raise ValueError(f"graph_spectrum: expected n_graphs >= 1 and n >= 1, got {n_graphs} and {n}")
+    if n > SPECTRUM_MAX_N:
+        raise ValueError(f"graph_spectrum: n = {n} > {SPECTRUM_MAX_N}")
+    if not 2 <= n_moments <= SPECTRUM_MAX_MOMENTS:
+        raise ValueError(f"graph_spectrum: expected 2 <= n_moments <= {SPECTRUM_MAX_MOMENTS}, got {n_moments}")
+    if n_probes is None:
+        n_probes = 0 if n <= SPECTRUM_EXACT_MAX_N else SPECTRUM_PROBES
+    n_probes, seed = int(n_probes), int(seed)
+    if n_probes < 0:
+        raise ValueError(f"graph_spectrum: expected n_probes >= 0, got {n_probes}")
+    if not 0 <= seed < (1 << 64):
+        raise ValueError(f"graph_spectrum: expected a 64-bit seed, got {seed}")
+    rows = n_graphs * n
+    # colidx may be empty (a generated graph without an edge): it is never read then
+    for t, name, numel in ((rowptr, "rowptr", rows + 1), (colidx, "colidx", 0)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() >= numel):
+            raise ValueError(f"graph_spectrum {name}: expected a contiguous int32 device tensor of >= {numel} elements")
+    dev = rowptr.device
+    moments = torch.empty(n_graphs, n_moments, dtype=torch.float64, device=dev)
+    info = torch.empty(n_graphs, 4, dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    cap = colidx.numel()
+    wsb = L.snd_graph_spectrum_workspace(n_graphs, n, cap)
+    if wsb == 0:
+        raise _lib.SNDError(f"snd_graph_spectrum_workspace: bad shape n_graphs={n_graphs} n={n}")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(L.snd_graph_spectrum(_P(rowptr), _P(colidx) if cap else 0, cap, n_graphs, n, n_moments, n_probes, seed,
+                                    1 if force_global else 0, _P(moments), _P(info), _P(ws), wsb, _lib.stream_ptr()),
+               "snd_graph_spectrum")
+    return moments, info
 
 
 def latent_mi(z, factors, n_bins=20, factor_bins=None, want_joint=False):

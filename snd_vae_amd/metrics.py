@@ -19,7 +19,8 @@ generated graphs and the data.
 ``PathStats`` is its companion for the graph as a network: components, hop distances
 and the detour of the network route over the straight line, from ``snd_graph_paths``.
 ``MotifStats`` is the 4-node side: the graphlet census of ``snd_graph_motifs``, its orbit
-vectors and their Gaussian-kernel MMD.
+vectors and their Gaussian-kernel MMD.  ``SpectrumStats`` is the global side: the spectral
+density of the normalised Laplacian from the Chebyshev moments of ``snd_graph_spectrum``.
 
 ``LatentMI`` (at the end) is the disentanglement side (`main.py:424`): MIG, avgMI,
 modularity and the per-group share of each factor's information, from the
@@ -986,6 +987,194 @@ class MotifStats:
 
     def __repr__(self) -> str:
         return f"MotifStats(n_graphs={self.n_graphs}, n={self.n})"
+
+
+# ---------------------------------------------------------------------------
+# Spectral density from the Chebyshev moments of ``snd_graph_spectrum``
+# ---------------------------------------------------------------------------
+def jackson_weights(n_moments: int) -> np.ndarray:
+    """g_k, k < K, of the Jackson kernel (Weisse et al., Rev. Mod. Phys. 78, 2006, eq. 71):
+    [(K - k + 1) cos(pi k / (K + 1)) + sin(pi k / (K + 1)) cot(pi / (K + 1))] / (K + 1)."""
+    K = int(n_moments)
+    k = np.arange(K, dtype=np.float64)
+    q = np.pi / (K + 1.0)
+    return ((K - k + 1.0) * np.cos(q * k) + np.sin(q * k) / np.tan(q)) / (K + 1.0)
+
+
+class SpectrumStats:
+    """moments [G, K] (float64) and info [G, 4] (int64) of a set of G graphs of n nodes each
+    (``layers.graph_spectrum`` / ``snd_graph_spectrum``): per graph the Chebyshev moments
+    mu_k = tr T_k(L - I) of the normalised Laplacian L of its mutual-edge graph (exact, or a
+    Hutchinson estimate over Rademacher probes) and {edges, isolated nodes, one-way arcs,
+    probes used}.  ``density`` rebuilds the eigenvalue histogram over [0, 2] by the kernel
+    polynomial method with the Jackson kernel: resolution pi / K, non-negative, total mass 1.
+
+    Same storage idiom as GraphStats / PathStats: NumPy arrays or torch tensors; device
+    tensors are read back once, on first use.
+    """
+
+    def __init__(self, moments, info, n: int):
+        self._dev = None
+        self._np = None
+        self.n = int(n)
+        if self.n < 1:
+            raise ValueError("SpectrumStats: n must be >= 1")
+        if _is_tensor(moments) != _is_tensor(info):
+            raise ValueError("SpectrumStats: moments and info must both be tensors or both arrays")
+        if _is_tensor(moments):
+            if moments.dim() != 2 or moments.shape[1] < 2 or tuple(info.shape) != (moments.shape[0], 4):
+                raise ValueError("SpectrumStats: expected moments [G, K >= 2] and info [G, 4]")
+            self._dev = (moments, info)
+        else:
+            m = np.asarray(moments, dtype=np.float64)
+            i = np.asarray(info, dtype=np.int64)
+            if m.ndim == 1:
+                m, i = m[None], i.reshape(1, -1)
+            if m.ndim != 2 or m.shape[1] < 2 or i.shape != (m.shape[0], 4):
+                raise ValueError("SpectrumStats: expected moments [G, K >= 2] and info [G, 4]")
+            self._np = (m, i)
+
+    # ---- storage
+    @property
+    def tensors(self):
+        """The (moments, info) torch tensors this object was built on, or None."""
+        return self._dev
+
+    def invalidate(self) -> None:
+        """Forget the host copy: the device tensors were written since it was read."""
+        if self._dev is not None:
+            self._np = None
+
+    def _arrays(self) -> Tuple[np.ndarray, np.ndarray]:
+        if self._np is None:
+            self._np = (self._dev[0].cpu().numpy().astype(np.float64, copy=False),
+                        self._dev[1].cpu().numpy().astype(np.int64, copy=False))
+        return self._np
+
+    @property
+    def moments(self) -> np.ndarray:
+        return self._arrays()[0]
+
+    @property
+    def info(self) -> np.ndarray:
+        return self._arrays()[1]
+
+    @property
+    def n_graphs(self) -> int:
+        return int((self._dev[0] if self._np is None else self._np[0]).shape[0])
+
+    @property
+    def n_moments(self) -> int:
+        return int((self._dev[0] if self._np is None else self._np[0]).shape[1])
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, SpectrumStats) and self.n == other.n
+                and np.array_equal(self.moments, other.moments) and np.array_equal(self.info, other.info))
+
+    __hash__ = None
+
+    @classmethod
+    def concat(cls, parts) -> "SpectrumStats":
+        """The graphs of several SpectrumStats (batches of one dataset) as one set, in order."""
+        parts = list(parts)
+        if not parts or not all(isinstance(p, SpectrumStats) for p in parts):
+            raise ValueError("SpectrumStats.concat: expected a non-empty list of SpectrumStats")
+        if any(p.n != parts[0].n or p.n_moments != parts[0].n_moments for p in parts):
+            raise ValueError("SpectrumStats.concat: the parts differ in n or in the number of moments")
+        return cls(np.concatenate([p.moments for p in parts]), np.concatenate([p.info for p in parts]), parts[0].n)
+
+    def all_gather(self, process_group=None) -> "SpectrumStats":
+        """Every rank's graphs as one set, in rank order (data parallel; each rank holds the
+        same number of graphs), as a new SpectrumStats: the same on every rank."""
+        import torch
+        import torch.distributed as dist
+        dev = self._dev[0].device if self._dev is not None else torch.device("cpu")
+        if dev.type == "cpu" and dist.get_backend(process_group) == "nccl":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        world = dist.get_world_size(process_group)
+        both = []
+        for x in (self.moments, self.info):
+            t = torch.from_numpy(x.copy()).to(dev)
+            out = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(out, t, group=process_group)
+            both.append(torch.cat(out))
+        return SpectrumStats(both[0], both[1], self.n)
+
+    # ---- descriptors
+    def density(self, bins: int = 200) -> np.ndarray:
+        """[G, bins] float64: the Jackson-damped spectral mass of each of ``bins`` equal-width
+        bins of lambda in [0, 2], integrated in closed form in theta = arccos(lambda - 1):
+
+            mass(a, b) = [g_0 mu_0 (theta_a - theta_b)
+                          + 2 sum_{k >= 1} g_k mu_k (sin k theta_a - sin k theta_b) / k] / (pi mu_0).
+
+        Rows are >= 0 (rounding noise below zero is clipped) and sum to 1."""
+        bins = int(bins)
+        if bins < 1:
+            raise ValueError("SpectrumStats.density: bins must be >= 1")
+        m = self.moments
+        K = m.shape[1]
+        theta = np.arccos(np.clip(np.linspace(0.0, 2.0, bins + 1) - 1.0, -1.0, 1.0))    # pi .. 0
+        k = np.arange(1, K, dtype=np.float64)
+        coef = m[:, 1:] * (jackson_weights(K)[1:] / k)[None, :]                        # [G, K - 1]
+        cum = theta[None, :] * m[:, :1] + 2.0 * coef @ np.sin(k[:, None] * theta[None, :])
+        mass = (cum[:, :-1] - cum[:, 1:]) / (np.pi * m[:, :1])
+        return np.maximum(mass, 0.0)
+
+    def pooled(self, bins: int = 200) -> np.ndarray:
+        """The mean density over the graphs of the set."""
+        return self.density(bins).mean(axis=0)
+
+    def second_moment(self) -> np.ndarray:
+        """[G]: tr(M^2) / N = (mu_2 + mu_0) / (2 mu_0) (T_2(x) = 2 x^2 - 1); nan with K < 3."""
+        m = self.moments
+        if m.shape[1] < 3:
+            return np.full(m.shape[0], NAN)
+        return (m[:, 2] + m[:, 0]) / (2.0 * m[:, 0])
+
+    def summary(self) -> dict:
+        """The set as a whole: n_graphs, n_moments, the mean share of isolated nodes, the mean
+        number of one-way arcs and the mean of tr(M^2) / N; nan without a graph."""
+        i = self.info
+        mean = lambda x: float(np.mean(x)) if x.size else NAN
+        return {"n_graphs": self.n_graphs, "n_moments": self.n_moments,
+                "mean_isolated_share": mean(i[:, 1] / float(self.n)), "mean_one_way": mean(i[:, 2].astype(np.float64)),
+                "mean_second_moment": mean(self.second_moment())}
+
+    # ---- two-sample statistics
+    def _check_other(self, other):
+        if not isinstance(other, SpectrumStats):
+            raise ValueError("SpectrumStats: expected another SpectrumStats")
+
+    def mmd(self, other: "SpectrumStats", sigma: float = 1.0, bins: int = 200) -> float:
+        """GraphStats.mmd's statistic (biased MMD^2, Gaussian kernel over the EMD in lambda
+        units) between the two sets' spectral densities: the spectral descriptor of GRAN's
+        evaluation (Liao et al., NeurIPS 2019), restated here on the reconstructed histograms."""
+        self._check_other(other)
+        sigma = float(sigma)
+        if not sigma > 0.0:
+            raise ValueError("SpectrumStats.mmd: sigma must be > 0")
+        return _emd_mmd(self.density(bins), other.density(bins), 2.0 / bins, sigma)
+
+    def kld(self, other: "SpectrumStats", eps: float = 1e-12, bins: int = 200) -> float:
+        """KL(self || other) of the pooled densities, each smoothed by eps per bin and
+        renormalised (scipy.stats.entropy(p + eps, q + eps)).  nan when either side is empty."""
+        self._check_other(other)
+        if self.n_graphs == 0 or other.n_graphs == 0:
+            return NAN
+        p, q = self.pooled(bins), other.pooled(bins)
+        p = (p + eps) / (p + eps).sum()
+        q = (q + eps) / (q + eps).sum()
+        return float(np.sum(p * np.log(p / q)))
+
+    def compare(self, other: "SpectrumStats") -> dict:
+        """{"mmd_spectrum", "kld_spectrum"} and both sides' summaries under "self" and "other"."""
+        self._check_other(other)
+        return {"mmd_spectrum": self.mmd(other), "kld_spectrum": self.kld(other), "self": self.summary(),
+                "other": other.summary()}
+
+    def __repr__(self) -> str:
+        return f"SpectrumStats(n_graphs={self.n_graphs}, n={self.n}, n_moments={self.n_moments})"
 
 
 class LatentMI:

@@ -239,7 +239,8 @@ class SGCNModelVAE:
                  z: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                  seed: int = 0, step: int = 0, want_adj: bool = True, stream=None,
                  adj_format: str = "dense", threshold: float = 0.0, inclusive: bool = False,
-                 stats: bool = False, paths: bool = False, src_step: int = 1, motifs: bool = False) -> dict:
+                 stats: bool = False, paths: bool = False, src_step: int = 1, motifs: bool = False,
+                 spectrum: bool = False) -> dict:
         """Forward-only decode (`main.py:358-469`, `model.py:163-169`).
 
         mode: "mean" (z = z_mean, reconstruction), "sample" (z = mu + eps e^s as
@@ -267,6 +268,9 @@ class SGCNModelVAE:
 
         motifs=True (CSR format only): also "generated_motifs", a metrics.MotifStats over the
         device census of the generated CSR (layers.graph_motifs at its default work_cap).
+
+        spectrum=True (CSR format only): also "generated_spectrum", a metrics.SpectrumStats over
+        the device Chebyshev moments of the generated CSR (layers.graph_spectrum at its defaults).
         """
         if adj_format not in ("dense", "csr"):
             raise ValueError(f"adj_format must be 'dense' or 'csr', got {adj_format!r}")
@@ -276,6 +280,8 @@ class SGCNModelVAE:
             raise ValueError("paths=True needs adj_format='csr': the statistics are taken from the CSR")
         if motifs and adj_format != "csr":
             raise ValueError("motifs=True needs adj_format='csr': the census is taken from the CSR")
+        if spectrum and adj_format != "csr":
+            raise ValueError("spectrum=True needs adj_format='csr': the moments are taken from the CSR")
         if adj_format == "dense" and (threshold != 0.0 or inclusive):
             raise ValueError("the dense generated_adj decides at L > 0 only: a threshold or "
                              "inclusive needs adj_format='csr'")
@@ -294,6 +300,8 @@ class SGCNModelVAE:
                     gpaths = self._graph_paths(rowptr, colidx, self.generated_spatial, src_step)
                 if motifs:
                     gmotifs = self._graph_motifs(rowptr, colidx)
+                if spectrum:
+                    gspectrum = self._graph_spectrum(rowptr, colidx)
         else:
             self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
         out = {"generated_adj": adj,
@@ -308,6 +316,8 @@ class SGCNModelVAE:
                 out["generated_paths"] = gpaths
             if motifs:
                 out["generated_motifs"] = gmotifs
+            if spectrum:
+                out["generated_spectrum"] = gspectrum
         if mode in ("mean", "sample"):
             out["z_mean"] = self.z_mean_sg.clone()
             out["z_std"] = self.z_std_sg.clone()
@@ -361,6 +371,22 @@ class SGCNModelVAE:
             raise ValueError("graph_motifs: the batch does not match the plan's shape")
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             return self._graph_motifs(batch.rowptr, batch.colidx)
+
+    def _graph_spectrum(self, rowptr, colidx):
+        """metrics.SpectrumStats over fresh device moments (current stream, no read-back)."""
+        from . import layers
+        from .metrics import SpectrumStats
+        moments, info = layers.graph_spectrum(rowptr, colidx, self.n_graphs, self.cfg.n_nodes)
+        return SpectrumStats(moments, info, self.cfg.n_nodes)
+
+    def graph_spectrum(self, batch: DeviceBatch, stream=None):
+        """Spectral density (metrics.SpectrumStats: Chebyshev moments of the normalised
+        Laplacian per graph, the Jackson-kernel eigenvalue histogram, MMD) of a batch's own
+        adjacency."""
+        if batch.n_graphs != self.n_graphs or batch.n_nodes != self.cfg.n_nodes:
+            raise ValueError("graph_spectrum: the batch does not match the plan's shape")
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return self._graph_spectrum(batch.rowptr, batch.colidx)
 
     def _generate_launch(self, batch, mode, z, eps, seed, step, adj, stream):
         """snd_generate on the plan's workspace (argument checks of generate())."""

@@ -172,7 +172,7 @@ class Trainer:
 
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
                             inclusive: bool = True, seed: int = 0, paths: bool = False,
-                            src_step: int = 1, motifs: bool = False) -> dict:
+                            src_step: int = 1, motifs: bool = False, spectrum: bool = False) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats: degree, local clustering and edge length per graph) of the
         batch itself and of a graph generated at its shape: mode "prior" decodes z ~ N(0, 1)
@@ -192,29 +192,37 @@ class Trainer:
 
         motifs=True adds "motifs": the ``metrics.MotifStats.compare`` (orbit MMD, mean 4-node
         graphlet frequencies) of the same two sets, with the two MotifStats under its
-        "dataset" and "generated"."""
-        from .metrics import GraphStats, MotifStats, PathStats
+        "dataset" and "generated".
+
+        spectrum=True adds "spectrum": the ``metrics.SpectrumStats.compare`` (MMD and KL
+        divergence of the spectral densities of the normalised Laplacian) of the same two sets,
+        with the two SpectrumStats under its "dataset" and "generated"."""
+        from .metrics import GraphStats, MotifStats, PathStats, SpectrumStats
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
             threshold = self.evaluate(mode)["best_f1_threshold"]
             if threshold != threshold:                  # no positive anywhere: nothing to tune on
                 raise ValueError("evaluate_generation: the dataset has no edge to choose a threshold by")
-        data, gen, pdata, pgen, mdata, mgen = [], [], [], [], [], []
+        data, gen, pdata, pgen, mdata, mgen, sdata, sgen = [], [], [], [], [], [], [], []
         for i, b in enumerate(self.batches):
             data.append(self.model.graph_stats(b))
             if paths:
                 pdata.append(self.model.graph_paths(b, src_step))
             if motifs:
                 mdata.append(self.model.graph_motifs(b))
+            if spectrum:
+                sdata.append(self.model.graph_spectrum(b))
             out = self.model.generate(b if mode == "mean" else None, mode=mode, seed=seed, step=i,
                                       adj_format="csr", threshold=threshold, inclusive=inclusive, stats=True,
-                                      paths=paths, src_step=src_step, motifs=motifs)
+                                      paths=paths, src_step=src_step, motifs=motifs, spectrum=spectrum)
             gen.append(out["generated_stats"])
             if paths:
                 pgen.append(out["generated_paths"])
             if motifs:
                 mgen.append(out["generated_motifs"])
+            if spectrum:
+                sgen.append(out["generated_spectrum"])
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         if self.opt.distributed:
             data, gen = data.all_gather(self.opt.group), gen.all_gather(self.opt.group)
@@ -230,6 +238,11 @@ class Trainer:
             if self.opt.distributed:
                 mdata, mgen = mdata.all_gather(self.opt.group), mgen.all_gather(self.opt.group)
             out["motifs"] = dict(mdata.compare(mgen), dataset=mdata, generated=mgen)
+        if spectrum:
+            sdata, sgen = SpectrumStats.concat(sdata), SpectrumStats.concat(sgen)
+            if self.opt.distributed:
+                sdata, sgen = sdata.all_gather(self.opt.group), sgen.all_gather(self.opt.group)
+            out["spectrum"] = dict(sdata.compare(sgen), dataset=sdata, generated=sgen)
         return out
 
     def save(self, path: str):
