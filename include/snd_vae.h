@@ -38,7 +38,7 @@ enum { SND_F32 = 0, SND_BF16 = 1 }; /* MFMA operand dtype; accumulation always f
 
 const char* snd_last_error(void);
 /* the ABI this header describes; snd_abi_version() returns it */
-#define SND_ABI_VERSION 28
+#define SND_ABI_VERSION 29
 int snd_abi_version(void);
 
 /* ---- a1: adjacency ingest ------------------------------------------------
@@ -466,6 +466,73 @@ int snd_graph_spectrum(const int* rowptr, const int* colidx, long long nnz_cap, 
                        int n_moments, int n_probes, unsigned long long seed, int flags,
                        double* moments, long long* info, void* workspace, size_t workspace_bytes,
                        snd_stream_t stream);
+
+/* ---- edge crossings of a CSR drawn at its coordinates (ABI 29; forward only) --------
+ * SND-VAE generates spatial networks: is a generated network drawn like the data?  Edge
+ * crossings are the canonical measure of how far a spatial network is from planar
+ * (Barthelemy, Spatial networks, Phys. Rep. 499 (2011), section 2.1), the distribution of
+ * edge directions is Boeing's orientation descriptor (Urban spatial order, Appl. Netw. Sci. 4
+ * (2019)).  B graphs x N nodes, 1 <= N <= 16384, B N < 2^31, from the block-diagonal CSR of
+ * this header's preamble.  coords [B N, ldc] fp32, ldc >= 2; only columns 0 and 1 are read (a
+ * 3-D caller passes the projection it wants).
+ *   The graph is snd_graph_motifs': N(i) = the columns of row i inside i's block, i itself
+ *   left out; {i, j} is an edge iff j in N(i) AND i in N(j); a one-way arc is no edge and is
+ *   counted apart; out-of-block entries and self loops are ignored; of duplicate entries the
+ *   first occurrence counts (effect unspecified, no fault, no store outside the outputs).  An
+ *   edge is written (a, b), a < b in local ids.
+ *   The predicate is the whole definition.  Two edges e = (a, b) and f = (c, d) CROSS iff
+ *     1. they share no endpoint;
+ *     2. their bounding boxes overlap, by fp32 compares on the coordinates as stored: no
+ *        crossing if max(ax, bx) < min(cx, dx), or the same with e and f swapped, or either of
+ *        these in y;
+ *     3. they straddle each other strictly: with orient(p, q, r) = (qx - px)(ry - py) -
+ *        (qy - py)(rx - px) evaluated in double from the fp32 coordinates, each of its four
+ *        differences, two products and the final subtraction rounded once (no contraction),
+ *        orient(a, b, c) and orient(a, b, d) are non-zero with opposite signs, and so are
+ *        orient(c, d, a) and orient(c, d, b).  Signs are compared, no product of orients is
+ *        formed.
+ *   Touching, T-junctions, collinear overlaps, coincident nodes and zero-length edges are
+ *   therefore not crossings; the conjunction is symmetric in e and f.
+ * work [B] int64, always written: E_b (E_b - 1) / 2, the pairs to test.  A graph with
+ *   work[b] > work_cap is NOT counted: its counts row is -1, its hist rows are 0, its
+ *   cross_out entries are -1; every other graph is unaffected.
+ * counts [B, 7] int64: {0: E edges, 1: X crossing pairs, 2: edges with >= 1 crossing,
+ *   3: independent pairs E (E - 1) / 2 - sum_v C(deg_v, 2) with deg in this graph (the
+ *   denominator of the crossing ratio), 4: one-way arcs, 5: zero-length edges (both
+ *   coordinates equal), 6: the largest crossing count of one edge}.
+ * hist [B, 3, 256] int64:
+ *   [0][min(c_e, 255)] += 1 per edge, c_e its crossing count;
+ *   [1][k] += 1 per edge of non-zero length, for its direction folded to [0, pi): u = b - a
+ *     per component (one fp32 rounding each), negated if uy < 0 or (uy == 0 and ux < 0),
+ *     theta = atan2f(uy, ux), k = floor(theta (256 / pi) + 0.5) mod 256 in fp32: the bins are
+ *     centred on 0, pi / 256, ..., so axis-aligned and diagonal edges fall in bin centres;
+ *   [2][k] += 1 per crossing pair, for the acute angle phi = atan2f(|ux vy - uy vx|,
+ *     |ux vx + uy vy|) in [0, pi / 2] (fp32, every operation rounded once),
+ *     k = min(floor(phi (512 / pi)), 255).
+ * cross_out [nnz_cap] int32, may be NULL: the entries p < rowptr[B N] that are a mutual edge
+ *   with global column > row hold c_e, every other such entry 0 (-1 in a skipped graph);
+ *   entries past rowptr[B N] are untouched.
+ *   work_cap has no default at this level: the caller passes it.  The Python binding's
+ *   default (layers.CROSSINGS_WORK_CAP = 4e11 pairs) is the rate measured on one MI355X on
+ *   10^5 long random edges, where nearly every pair reaches the double predicate and a quarter
+ *   cross, 3.7e11 pairs per second, to one digit: about a second for a graph at the cap.  On
+ *   the N = 4096 bench graphs, where the box test rejects nearly every pair, the op ran 1.6e12
+ *   pairs per second (tools/graph_crossings_timing.py, profiles/graph_crossings_timing.json).
+ * Every call overwrites the outputs (no accumulate mode).  Integer atomics only, no
+ * allocation, no host synchronisation; the launch count and every grid size depend only on
+ * (B, N, nnz_cap); two runs are bitwise equal and a HIP-graph replay equals the eager call.
+ * Non-finite coordinates: unspecified counts, no fault, no store outside the outputs.
+ * SND_ERR_ARG before anything is launched, buffers untouched: n_graphs < 1; n < 1 or
+ * n > 16384; B N >= 2^31; nnz_cap < 0; work_cap < 0; ldc < 2; NULL rowptr, coords, counts,
+ * hist or work; NULL colidx with nnz_cap > 0; a workspace that is NULL, not 16-byte aligned
+ * or below snd_graph_crossings_workspace() bytes (64 B per graph of sums, 8 (B + 1) B of
+ * tile-pair prefix, each rounded up to 16 bytes, and 28 B per entry of max(nnz_cap, 1)
+ * rounded up to 4 entries: the edge list; 0 for a shape the op rejects). */
+size_t snd_graph_crossings_workspace(int n_graphs, int n, long long nnz_cap);
+int snd_graph_crossings(const int* rowptr, const int* colidx, long long nnz_cap, int n_graphs, int n,
+                        const float* coords, int ldc, long long work_cap,
+                        long long* counts, long long* hist, long long* work, int* cross_out,
+                        void* workspace, size_t workspace_bytes, snd_stream_t stream);
 
 /* ---- a11: sigmoid head + MSE ----------------------------------------------
  * Replaces tf.nn.sigmoid(linear(...)) (model_joint.py:121,144) and the

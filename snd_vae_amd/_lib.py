@@ -17,7 +17,7 @@ c_int, c_ll, c_float, c_size, c_ull = C.c_int, C.c_longlong, C.c_float, C.c_size
 vp = C.c_void_p
 
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 GEN_MODES = {"sample": 0, "mean": 1, "prior": 2, "given": 3}
 TOPOLOGY = {"tscale": 0, "tref": 1, "sgjoint": 2}
 
@@ -123,6 +123,8 @@ _SIGS = {
     "snd_graph_motifs": (c_int, [vp, vp, c_ll, c_int, c_int, c_ll, vp, vp, vp, c_size, vp]),
     "snd_graph_spectrum_workspace": (c_size, [c_int, c_int, c_ll]),
     "snd_graph_spectrum": (c_int, [vp, vp, c_ll, c_int, c_int, c_int, c_int, c_ull, c_int, vp, vp, vp, c_size, vp]),
+    "snd_graph_crossings_workspace": (c_size, [c_int, c_int, c_ll]),
+    "snd_graph_crossings": (c_int, [vp, vp, c_ll, c_int, c_int, vp, c_int, c_ll, vp, vp, vp, vp, vp, c_size, vp]),
     "snd_sigmoid_mse_blocks": (c_int, [c_int]),
     "snd_sigmoid_mse": (c_int, [vp, c_int, c_int, c_int, vp, vp, c_int, vp, c_int, vp, vp,
                                 vp, c_int, vp, vp, vp, c_size, vp]),

@@ -248,7 +248,8 @@ class DisentTrainer:
 
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
                             inclusive: bool = True, seed: int = 0, paths: bool = False,
-                            src_step: int = 1, motifs: bool = False, spectrum: bool = False) -> dict:
+                            src_step: int = 1, motifs: bool = False, spectrum: bool = False,
+                            crossings: bool = False) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats) of the batch itself (its CSR and coordinates) and of a graph
         generated at its shape: mode "prior" decodes z ~ N(0, 1) (test_generation,
@@ -275,8 +276,15 @@ class DisentTrainer:
         spectrum=True adds "spectrum": the ``metrics.SpectrumStats.compare`` (MMD and KL
         divergence of the spectral densities of the normalised Laplacian;
         ``layers.graph_spectrum`` at its defaults) of the same two sets, with the two
-        SpectrumStats under its "dataset" and "generated"."""
-        from .metrics import GraphStats, MotifStats, PathStats, SpectrumStats
+        SpectrumStats under its "dataset" and "generated".
+
+        crossings=True (spatial_dim 2) adds "crossings": the ``metrics.CrossingStats.compare``
+        (edge crossings as drawn, edge directions, crossing angles; ``layers.graph_crossings``
+        at its default work_cap) of the same two sets, each at its own coordinates, with the
+        two CrossingStats under its "dataset" and "generated"."""
+        from .metrics import CrossingStats, GraphStats, MotifStats, PathStats, SpectrumStats
+        if crossings and self.cfg.spatial_dim != 2:
+            raise ValueError(f"evaluate_generation: crossings=True needs spatial_dim 2, got {self.cfg.spatial_dim}")
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
@@ -287,6 +295,7 @@ class DisentTrainer:
         max_len = math.sqrt(sd)
         scale = self.PATH_DETOUR_SCALE
         data, gen, csr, pdata, pgen, mdata, mgen, sdata, sgen = [], [], [], [], [], [], [], [], []
+        xdata, xgen = [], []
         for i, b in enumerate(self.batches):
             data.append(GraphStats(*layers.graph_stats(b.rowptr, b.colidx, B, N, b.spatial, max_len), N, max_len))
             if paths:
@@ -296,6 +305,8 @@ class DisentTrainer:
                 mdata.append(MotifStats(layers.graph_motifs(b.rowptr, b.colidx, B, N)[0], N))
             if spectrum:
                 sdata.append(SpectrumStats(*layers.graph_spectrum(b.rowptr, b.colidx, B, N), N))
+            if crossings:
+                xdata.append(CrossingStats(*layers.graph_crossings(b.rowptr, b.colidx, B, N, b.spatial)[:2], N))
             out = self.model.generate(b, z=mode, seed=seed + i, want_margin=True)
             m = out["margin"]
             dense = ((m >= threshold) if inclusive else (m > threshold)).float()   # the diagonal is ignored
@@ -309,6 +320,8 @@ class DisentTrainer:
                 mgen.append(MotifStats(layers.graph_motifs(rowptr, colidx, B, N)[0], N))
             if spectrum:
                 sgen.append(SpectrumStats(*layers.graph_spectrum(rowptr, colidx, B, N), N))
+            if crossings:
+                xgen.append(CrossingStats(*layers.graph_crossings(rowptr, colidx, B, N, coords)[:2], N))
             csr.append((rowptr, colidx))
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         out = data.compare(gen)
@@ -322,6 +335,9 @@ class DisentTrainer:
         if spectrum:
             sdata, sgen = SpectrumStats.concat(sdata), SpectrumStats.concat(sgen)
             out["spectrum"] = dict(sdata.compare(sgen), dataset=sdata, generated=sgen)
+        if crossings:
+            xdata, xgen = CrossingStats.concat(xdata), CrossingStats.concat(xgen)
+            out["crossings"] = dict(xdata.compare(xgen), dataset=xdata, generated=xgen)
         return out
 
     def evaluate_disentanglement(self, n_bins: int = 20, factor_bins: Optional[int] = None) -> dict:

@@ -26,6 +26,13 @@ MOTIFS_MAX_N = 16384             # snd_graph_motifs: local ids are 16-bit on chi
 # (tools/graph_motifs_timing.py), so a graph at this cap takes about a second.
 MOTIFS_WORK_CAP = 200_000_000_000
 SPECTRUM_MAX_N = 16384           # snd_graph_spectrum
+CROSSINGS_MAX_N = 16384          # snd_graph_crossings: local ids are 16-bit on chip
+CROSSINGS_TILE = 64              # kGxTile: edges per tile of the all-pairs kernel
+# Default work_cap of graph_crossings, in edge pairs: the op ran 3.7e11 pairs per second on 10^5 long
+# random edges, where nearly every pair reaches the double predicate and a quarter cross
+# (tools/graph_crossings_timing.py, "chords"; 1.6e12 on the bench graphs), so a graph at this cap
+# takes about a second at the slower rate.
+CROSSINGS_WORK_CAP = 400_000_000_000
 SPECTRUM_MAX_MOMENTS = 512
 SPECTRUM_EXACT_MAX_N = 256       # graph_spectrum's default: exact traces up to here ...
 SPECTRUM_PROBES = 32             # ... and this many Rademacher probes above
@@ -517,6 +524,60 @@ def graph_spectrum(rowptr, colidx, n_graphs, n, n_moments=128, n_probes=None, se
                                     1 if force_global else 0, _P(moments), _P(info), _P(ws), wsb, _lib.stream_ptr()),
                "snd_graph_spectrum")
     return moments, info
+
+
+def graph_crossings(rowptr, colidx, n_graphs, n, coords, work_cap=None, per_edge=False):
+    """Edge crossings of a block-diagonal CSR drawn at ``coords`` (snd_graph_crossings), nothing
+    read back.
+
+    rowptr / colidx: int32 device tensors as ``DeviceBatch`` holds and ``zzt_edges`` /
+    ``dense_to_csr`` return them; the graph is ``graph_motifs``' ({i, j} an edge iff both arcs
+    are present; out-of-block entries and self loops ignored).  coords: float32 device tensor
+    [n_graphs * n, >= 2] with unit column stride; columns 0 and 1 are read.  Two edges cross iff
+    they share no endpoint, their boxes overlap and they straddle each other strictly (the
+    header has the predicate: touching and collinear overlap are no crossings).  Returns
+    (counts, hist, work[, cross_out]): int64 device tensors [n_graphs, 7] = {E, X crossing
+    pairs, crossed edges, independent pairs, one-way arcs, zero-length edges, largest count of
+    one edge}, [n_graphs, 3, 256] = {edges by crossing count, edges by direction folded to
+    [0, pi), crossing pairs by acute angle} and [n_graphs] = E (E - 1) / 2; with ``per_edge``
+    also int32 [colidx.numel()]: c_e at the entry (row a, column b > a) of every edge, 0 at the
+    other entries below rowptr[-1].  A graph with work > ``work_cap`` (default
+    CROSSINGS_WORK_CAP) is not counted: its counts row and cross_out entries are -1, its hist
+    rows 0.  ``metrics.CrossingStats`` turns counts and hist into planarity, crossing ratio and
+    orientation entropy.  No host synchronisation."""
+    if n_graphs < 1 or n < 1:
+        raise ValueError(f"graph_crossings: expected n_graphs >= 1 and n >= 1, got {n_graphs} and {n}")
+    if n > CROSSINGS_MAX_N:
+        raise ValueError(f"graph_crossings: n = {n} > {CROSSINGS_MAX_N}")
+    work_cap = CROSSINGS_WORK_CAP if work_cap is None else int(work_cap)
+    if work_cap < 0:
+        raise ValueError(f"graph_crossings: expected work_cap >= 0, got {work_cap}")
+    rows = n_graphs * n
+    # colidx may be empty (a generated graph without an edge): it is never read then
+    for t, name, numel in ((rowptr, "rowptr", rows + 1), (colidx, "colidx", 0)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() >= numel):
+            raise ValueError(f"graph_crossings {name}: expected a contiguous int32 device tensor of >= {numel} "
+                             "elements")
+    if not (coords is not None and coords.is_cuda and coords.dtype == torch.float32 and coords.dim() == 2
+            and coords.shape[0] == rows and coords.shape[1] >= 2 and coords.stride(1) == 1):
+        raise ValueError(f"graph_crossings coords: expected a float32 device tensor [{rows}, >= 2] with unit "
+                         "column stride")
+    ldc = coords.stride(0) if rows > 1 else max(coords.shape[1], coords.stride(0))
+    dev = rowptr.device
+    counts = torch.empty(n_graphs, 7, dtype=torch.int64, device=dev)
+    hist = torch.empty(n_graphs, 3, 256, dtype=torch.int64, device=dev)
+    work = torch.empty(n_graphs, dtype=torch.int64, device=dev)
+    cap = colidx.numel()
+    cross = torch.zeros(cap, dtype=torch.int32, device=dev) if per_edge else None
+    L = _lib.lib()
+    wsb = L.snd_graph_crossings_workspace(n_graphs, n, cap)
+    if wsb == 0:
+        raise _lib.SNDError(f"snd_graph_crossings_workspace: bad shape n_graphs={n_graphs} n={n}")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(L.snd_graph_crossings(_P(rowptr), _P(colidx) if cap else 0, cap, n_graphs, n, _P(coords), ldc,
+                                     work_cap, _P(counts), _P(hist), _P(work), _P(cross), _P(ws), wsb,
+                                     _lib.stream_ptr()), "snd_graph_crossings")
+    return (counts, hist, work, cross) if per_edge else (counts, hist, work)
 
 
 def latent_mi(z, factors, n_bins=20, factor_bins=None, want_joint=False):

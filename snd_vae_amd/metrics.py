@@ -1177,6 +1177,273 @@ class SpectrumStats:
         return f"SpectrumStats(n_graphs={self.n_graphs}, n={self.n}, n_moments={self.n_moments})"
 
 
+# ---------------------------------------------------------------------------
+# Edge crossings and edge directions from the counters of ``snd_graph_crossings``
+# ---------------------------------------------------------------------------
+CROSSING_KINDS = ("crossings", "orientation", "cross_angle")
+CROSSING_NAMES = ("E", "X", "crossed", "independent", "one_way", "zero_length", "max_c")
+ORIENTATION_BINS = 32
+
+
+def orientation_entropy(h: np.ndarray) -> np.ndarray:
+    """Shannon entropy (nats) of the directions hist [..., 256] (bins centred on k pi / 256) over
+    ORIENTATION_BINS = 32 bins centred on j pi / 32: fine bin k goes to ((k + 4) mod 256) // 8, so
+    axis-aligned and diagonal edges sit in the centre of a coarse bin, as Boeing shifts his bins
+    (Urban spatial order, Appl. Netw. Sci. 4 (2019), section 3.2).  nan without an edge."""
+    h = np.asarray(h, dtype=np.float64)
+    w = GS_BINS // ORIENTATION_BINS
+    coarse = np.roll(h, w // 2, axis=-1).reshape(h.shape[:-1] + (ORIENTATION_BINS, w)).sum(axis=-1)
+    p = _normalised(coarse)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ent = -np.where(p > 0, p * np.log(np.where(p > 0, p, 1.0)), 0.0).sum(axis=-1)
+    return np.where(coarse.sum(axis=-1) > 0, ent, NAN)
+
+
+def orientation_order(entropy) -> np.ndarray:
+    """Boeing's orientation order phi = 1 - ((H - H_g) / (H_max - H_g))^2 (Boeing 2019, eq. 2)
+    restated for directions folded to [0, pi): a perfect grid has two of the 32 bins, so
+    H_g = ln 2 and H_max = ln 32 (his unfolded bearings: 4 of 36 bins).  1 for a grid, 0 for
+    uniform directions."""
+    e = np.asarray(entropy, dtype=np.float64)
+    return 1.0 - ((e - math.log(2.0)) / (math.log(ORIENTATION_BINS) - math.log(2.0))) ** 2
+
+
+class CrossingStats:
+    """counts [G, 7] and hist [G, 3, 256] of a set of G graphs of n nodes each
+    (``layers.graph_crossings`` / ``snd_graph_crossings``): per graph counts = {E edges, X
+    crossing pairs, edges with a crossing, independent pairs (the pairs of edges without a
+    common node), one-way arcs ignored, zero-length edges, the largest crossing count of one
+    edge} and the histograms of the per-edge crossing count (bin = min(c, 255)), of the edge
+    direction folded to [0, pi) (256 bins centred on k pi / 256) and of the acute angle of every
+    crossing pair (256 bins over [0, pi / 2]).  A graph that was not counted (its E (E - 1) / 2
+    pairs exceeded ``work_cap``) holds -1 in counts and is left out of every statistic below.
+
+    Is a generated spatial network drawn like the data: is it planar as embedded, how many of
+    its edges cross (Barthelemy, Spatial networks, Phys. Rep. 499 (2011), section 2.1), do its
+    edges follow the data's directions (Boeing 2019)?  Same storage idiom as GraphStats: NumPy
+    arrays or two int64 torch tensors, device tensors read back once, on first use.
+    """
+
+    def __init__(self, counts, hist, n: int):
+        self._dev = None
+        self._np = None
+        self.n = int(n)
+        if self.n < 1:
+            raise ValueError("CrossingStats: n must be >= 1")
+        if _is_tensor(counts):
+            if (counts.dim() != 2 or counts.shape[1] != 7
+                    or tuple(hist.shape) != (counts.shape[0], 3, GS_BINS)):
+                raise ValueError("CrossingStats: expected counts [G, 7] and hist [G, 3, 256]")
+            self._dev = (counts, hist)
+        else:
+            c = np.asarray(counts, dtype=np.int64)
+            h = np.asarray(hist, dtype=np.int64)
+            if c.ndim == 1:
+                c, h = c[None], h[None]
+            if c.ndim != 2 or c.shape[1] != 7 or h.shape != (c.shape[0], 3, GS_BINS):
+                raise ValueError("CrossingStats: expected counts [G, 7] and hist [G, 3, 256]")
+            self._np = (c, h)
+
+    # ---- storage
+    @property
+    def tensors(self):
+        """The (counts, hist) torch tensors this object was built on, or None."""
+        return self._dev
+
+    def invalidate(self) -> None:
+        """Forget the host copy: the device tensors were written since it was read."""
+        if self._dev is not None:
+            self._np = None
+
+    def _arrays(self) -> Tuple[np.ndarray, np.ndarray]:
+        if self._np is None:
+            import torch
+            c, h = self._dev
+            both = torch.cat([c.reshape(-1), h.reshape(-1)]).cpu().numpy()     # one read-back
+            k = c.numel()
+            self._np = (both[:k].reshape(tuple(c.shape)), both[k:].reshape(tuple(h.shape)))
+        return self._np
+
+    @property
+    def counts(self) -> np.ndarray:
+        return self._arrays()[0]
+
+    @property
+    def hist(self) -> np.ndarray:
+        return self._arrays()[1]
+
+    @property
+    def n_graphs(self) -> int:
+        """All graphs of the set, skipped ones included."""
+        return int((self._dev[0] if self._np is None else self._np[0]).shape[0])
+
+    @property
+    def counted(self) -> np.ndarray:
+        """[G] bool: the graphs that were counted."""
+        return self.counts[:, 0] >= 0
+
+    @property
+    def n_skipped(self) -> int:
+        return int((~self.counted).sum())
+
+    @property
+    def one_way(self) -> int:
+        """One-way arcs ignored, over the counted graphs."""
+        return int(self.counts[self.counted, 4].sum())
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, CrossingStats) and self.n == other.n
+                and np.array_equal(self.counts, other.counts) and np.array_equal(self.hist, other.hist))
+
+    __hash__ = None
+
+    @classmethod
+    def concat(cls, parts) -> "CrossingStats":
+        """The graphs of several CrossingStats (batches of one dataset) as one set, in order."""
+        parts = list(parts)
+        if not parts or not all(isinstance(p, CrossingStats) for p in parts):
+            raise ValueError("CrossingStats.concat: expected a non-empty list of CrossingStats")
+        if any(p.n != parts[0].n for p in parts):
+            raise ValueError("CrossingStats.concat: the parts differ in n")
+        return cls(np.concatenate([p.counts for p in parts]), np.concatenate([p.hist for p in parts]), parts[0].n)
+
+    def all_gather(self, process_group=None) -> "CrossingStats":
+        """Every rank's graphs as one set, in rank order (data parallel; each rank holds the
+        same number of graphs), as a new CrossingStats: the same on every rank."""
+        import torch
+        import torch.distributed as dist
+        dev = self._dev[0].device if self._dev is not None else torch.device("cpu")
+        if dev.type == "cpu" and dist.get_backend(process_group) == "nccl":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if self._dev is not None and self._dev[0].device == dev:
+            c, h = self._dev
+        else:
+            c = torch.from_numpy(self.counts.copy()).to(dev)
+            h = torch.from_numpy(self.hist.copy()).to(dev)
+        flat = torch.cat([c.reshape(-1), h.reshape(-1)])
+        out = [torch.empty_like(flat) for _ in range(dist.get_world_size(process_group))]
+        dist.all_gather(out, flat, group=process_group)
+        k = c.numel()
+        return CrossingStats(torch.cat([o[:k].reshape(c.shape) for o in out]),
+                             torch.cat([o[k:].reshape(h.shape) for o in out]), self.n)
+
+    # ---- bins
+    def _kind(self, kind: str):
+        """(row of hist, bin width in the statistic's own units, default sigma)."""
+        if kind == "crossings":
+            return 0, 1.0, 1.0                                   # crossings of one edge
+        if kind == "orientation":
+            return 1, math.pi / GS_BINS, 0.25                    # radians, the histogram cut at 0
+        if kind == "cross_angle":
+            return 2, math.pi / (2 * GS_BINS), 0.25              # radians
+        raise ValueError(f"CrossingStats: kind must be one of {CROSSING_KINDS}, got {kind!r}")
+
+    # ---- scalar properties
+    @staticmethod
+    def _scalars(c: np.ndarray, h: np.ndarray) -> dict:
+        c = c.astype(np.float64)
+        E, X = c[:, 0], c[:, 1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = lambda a, b: np.where(b > 0, a / np.where(b > 0, b, 1.0), NAN)
+            centres = (np.arange(GS_BINS, dtype=np.float64) + 0.5) * (math.pi / (2 * GS_BINS))
+            ent = orientation_entropy(h[:, 1, :])
+            return {"planar": (X == 0).astype(np.float64), "crossings_per_edge": ratio(X, E),
+                    "crossing_ratio": ratio(X, c[:, 3]), "crossed_share": ratio(c[:, 2], E),
+                    "orientation_entropy": ent, "orientation_order": orientation_order(ent),
+                    "mean_cross_angle": ratio((h[:, 2, :] * centres).sum(axis=1), h[:, 2, :].sum(axis=1))}
+
+    def per_graph(self) -> dict:
+        """{name: array over the counted graphs}: the seven counts (int64) and
+
+        * planar = 1.0 where X = 0: planar as drawn (a straight-line drawing without a crossing);
+        * crossings_per_edge = X / E; crossing_ratio = X / independent pairs, the share of the
+          pairs of edges that could cross that do; crossed_share = crossed edges / E;
+        * orientation_entropy H (nats, 32 bins, ``orientation_entropy``) and orientation_order
+          phi = 1 - ((H - ln 2) / (ln 32 - ln 2))^2 (``orientation_order``: Boeing 2019, eq. 2,
+          restated for folded directions);
+        * mean_cross_angle (radians, from the bin centres of the 256 bins over [0, pi / 2]).
+
+        nan where a ratio has no denominator."""
+        keep = self.counted
+        c, h = self.counts[keep], self.hist[keep]
+        out = {k: c[:, i] for i, k in enumerate(CROSSING_NAMES)}
+        out.update(self._scalars(c, h))
+        return out
+
+    def summary(self) -> dict:
+        """The set as a whole, as floats: planar is the share of the counted graphs with X = 0;
+        the ratios, the orientation entropy and order and the mean crossing angle are those of
+        the pooled counters (every edge of every graph weighs the same); n_skipped and one_way
+        are counts.  nan where nothing was counted."""
+        keep = self.counted
+        out = {"n_skipped": self.n_skipped, "one_way": self.one_way}
+        names = ("planar", "crossings_per_edge", "crossing_ratio", "crossed_share", "orientation_entropy",
+                 "orientation_order", "mean_cross_angle")
+        if not keep.any():
+            out.update({k: NAN for k in names})
+            return out
+        c, h = self.counts[keep], self.hist[keep]
+        pooled = self._scalars(c.sum(axis=0, keepdims=True), h.sum(axis=0, keepdims=True))
+        out.update({k: float(pooled[k][0]) for k in names})
+        out["planar"] = float((c[:, 1] == 0).mean())
+        return out
+
+    planar = property(lambda self: self.summary()["planar"])
+    crossing_ratio = property(lambda self: self.summary()["crossing_ratio"])
+
+    # ---- two-sample statistics
+    def _check_other(self, other, kind):
+        if not isinstance(other, CrossingStats):
+            raise ValueError("CrossingStats: expected another CrossingStats")
+        return self._kind(kind)
+
+    def mmd(self, other: "CrossingStats", kind: str, sigma=None) -> float:
+        """Biased (V-statistic) MMD^2 between two sets of graphs over their per-graph normalised
+        histograms of ``kind``, with GraphStats.mmd's kernel k = exp(-EMD^2 / (2 sigma^2)), the
+        EMD in the statistic's own units (crossings of an edge; radians, the circular direction
+        histogram cut at 0).  Default sigma: 1.0 crossing, 0.25 rad.  Skipped graphs are left
+        out; a graph without an edge or a crossing enters as the zero histogram."""
+        row, width, s0 = self._check_other(other, kind)
+        sigma = s0 if sigma is None else float(sigma)
+        if not sigma > 0.0:
+            raise ValueError("CrossingStats.mmd: sigma must be > 0")
+        return _emd_mmd(self.hist[self.counted][:, row, :], other.hist[other.counted][:, row, :], width, sigma)
+
+    def pooled(self, kind: str) -> np.ndarray:
+        """The normalised histogram of ``kind`` over the counted graphs of the set."""
+        row, _, _ = self._kind(kind)
+        return _normalised(self.hist[self.counted][:, row, :].sum(axis=0))
+
+    def kld(self, other: "CrossingStats", kind: str, eps: float = 1e-12) -> float:
+        """KL(self || other) of the pooled normalised histograms, smoothed as GraphStats.kld
+        (eps per bin, renormalised).  nan when either side has no count."""
+        self._check_other(other, kind)
+        p, q = self.pooled(kind), other.pooled(kind)
+        if p.sum() == 0 or q.sum() == 0:
+            return NAN
+        p = (p + eps) / (p + eps).sum()
+        q = (q + eps) / (q + eps).sum()
+        return float(np.sum(p * np.log(p / q)))
+
+    def compare(self, other: "CrossingStats") -> dict:
+        """mmd_<kind> and kld_<kind> for "crossings", "orientation" and "cross_angle", both
+        sides' summaries under "self" and "other" and the graphs left out under "n_skipped"
+        (self, other)."""
+        if not isinstance(other, CrossingStats):
+            raise ValueError("CrossingStats.compare: expected another CrossingStats")
+        out = {}
+        for kind in CROSSING_KINDS:
+            out[f"mmd_{kind}"] = self.mmd(other, kind)
+            out[f"kld_{kind}"] = self.kld(other, kind)
+        out["n_skipped"] = (self.n_skipped, other.n_skipped)
+        out["self"] = self.summary()
+        out["other"] = other.summary()
+        return out
+
+    def __repr__(self) -> str:
+        return f"CrossingStats(n_graphs={self.n_graphs}, n={self.n}, n_skipped={self.n_skipped})"
+
+
 class LatentMI:
     """mi [L, K], hz [L] and hf [K] of ``layers.latent_mi`` / ``snd_latent_mi``: the mutual
     information (nats) between every latent dimension and every generative factor and the

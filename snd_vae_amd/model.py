@@ -240,7 +240,7 @@ class SGCNModelVAE:
                  seed: int = 0, step: int = 0, want_adj: bool = True, stream=None,
                  adj_format: str = "dense", threshold: float = 0.0, inclusive: bool = False,
                  stats: bool = False, paths: bool = False, src_step: int = 1, motifs: bool = False,
-                 spectrum: bool = False) -> dict:
+                 spectrum: bool = False, crossings: bool = False) -> dict:
         """Forward-only decode (`main.py:358-469`, `model.py:163-169`).
 
         mode: "mean" (z = z_mean, reconstruction), "sample" (z = mu + eps e^s as
@@ -271,6 +271,10 @@ class SGCNModelVAE:
 
         spectrum=True (CSR format only): also "generated_spectrum", a metrics.SpectrumStats over
         the device Chebyshev moments of the generated CSR (layers.graph_spectrum at its defaults).
+
+        crossings=True (CSR format only, spatial_dim 2): also "generated_crossings", a
+        metrics.CrossingStats over the device counters of the generated CSR drawn at
+        generated_spatial (layers.graph_crossings at its default work_cap).
         """
         if adj_format not in ("dense", "csr"):
             raise ValueError(f"adj_format must be 'dense' or 'csr', got {adj_format!r}")
@@ -282,6 +286,11 @@ class SGCNModelVAE:
             raise ValueError("motifs=True needs adj_format='csr': the census is taken from the CSR")
         if spectrum and adj_format != "csr":
             raise ValueError("spectrum=True needs adj_format='csr': the moments are taken from the CSR")
+        if crossings and adj_format != "csr":
+            raise ValueError("crossings=True needs adj_format='csr': the edges are taken from the CSR")
+        if crossings and self.cfg.spatial_dim != 2:
+            raise ValueError(f"crossings=True needs spatial_dim 2, got {self.cfg.spatial_dim}: project the "
+                             "coordinates and call layers.graph_crossings")
         if adj_format == "dense" and (threshold != 0.0 or inclusive):
             raise ValueError("the dense generated_adj decides at L > 0 only: a threshold or "
                              "inclusive needs adj_format='csr'")
@@ -302,6 +311,8 @@ class SGCNModelVAE:
                     gmotifs = self._graph_motifs(rowptr, colidx)
                 if spectrum:
                     gspectrum = self._graph_spectrum(rowptr, colidx)
+                if crossings:
+                    gcrossings = self._graph_crossings(rowptr, colidx, self.generated_spatial)
         else:
             self._generate_launch(batch, mode, z, eps, seed, step, adj, stream)
         out = {"generated_adj": adj,
@@ -318,6 +329,8 @@ class SGCNModelVAE:
                 out["generated_motifs"] = gmotifs
             if spectrum:
                 out["generated_spectrum"] = gspectrum
+            if crossings:
+                out["generated_crossings"] = gcrossings
         if mode in ("mean", "sample"):
             out["z_mean"] = self.z_mean_sg.clone()
             out["z_std"] = self.z_std_sg.clone()
@@ -387,6 +400,24 @@ class SGCNModelVAE:
             raise ValueError("graph_spectrum: the batch does not match the plan's shape")
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             return self._graph_spectrum(batch.rowptr, batch.colidx)
+
+    def _graph_crossings(self, rowptr, colidx, coords):
+        """metrics.CrossingStats over fresh device counters (current stream, no read-back)."""
+        from . import layers
+        from .metrics import CrossingStats
+        if self.cfg.spatial_dim != 2:
+            raise ValueError(f"graph_crossings needs spatial_dim 2, got {self.cfg.spatial_dim}: project the "
+                             "coordinates and call layers.graph_crossings")
+        counts, hist, _ = layers.graph_crossings(rowptr, colidx, self.n_graphs, self.cfg.n_nodes, coords)
+        return CrossingStats(counts, hist, self.cfg.n_nodes)
+
+    def graph_crossings(self, batch: DeviceBatch, stream=None):
+        """Edge crossings (metrics.CrossingStats: planarity as drawn, crossing ratio,
+        orientation entropy, crossing angles) of a batch's own adjacency at ``spatial_truth``."""
+        if batch.n_graphs != self.n_graphs or batch.n_nodes != self.cfg.n_nodes:
+            raise ValueError("graph_crossings: the batch does not match the plan's shape")
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            return self._graph_crossings(batch.rowptr, batch.colidx, batch.spatial_truth)
 
     def _generate_launch(self, batch, mode, z, eps, seed, step, adj, stream):
         """snd_generate on the plan's workspace (argument checks of generate())."""

@@ -172,7 +172,8 @@ class Trainer:
 
     def evaluate_generation(self, mode: str = "prior", threshold: Optional[float] = None,
                             inclusive: bool = True, seed: int = 0, paths: bool = False,
-                            src_step: int = 1, motifs: bool = False, spectrum: bool = False) -> dict:
+                            src_step: int = 1, motifs: bool = False, spectrum: bool = False,
+                            crossings: bool = False) -> dict:
         """Do generated graphs look like the data?  For every batch the graph statistics
         (metrics.GraphStats: degree, local clustering and edge length per graph) of the
         batch itself and of a graph generated at its shape: mode "prior" decodes z ~ N(0, 1)
@@ -196,8 +197,15 @@ class Trainer:
 
         spectrum=True adds "spectrum": the ``metrics.SpectrumStats.compare`` (MMD and KL
         divergence of the spectral densities of the normalised Laplacian) of the same two sets,
-        with the two SpectrumStats under its "dataset" and "generated"."""
-        from .metrics import GraphStats, MotifStats, PathStats, SpectrumStats
+        with the two SpectrumStats under its "dataset" and "generated".
+
+        crossings=True (spatial_dim 2) adds "crossings": the ``metrics.CrossingStats.compare``
+        (edge crossings as drawn, edge directions, crossing angles) of the same two sets, the
+        data at ``spatial_truth`` and the generated graphs at their generated coordinates, with
+        the two CrossingStats under its "dataset" and "generated"."""
+        from .metrics import CrossingStats, GraphStats, MotifStats, PathStats, SpectrumStats
+        if crossings and self.cfg.spatial_dim != 2:
+            raise ValueError(f"evaluate_generation: crossings=True needs spatial_dim 2, got {self.cfg.spatial_dim}")
         if mode not in ("prior", "mean"):
             raise ValueError(f"evaluate_generation: mode must be 'prior' or 'mean', got {mode!r}")
         if threshold is None:
@@ -205,6 +213,7 @@ class Trainer:
             if threshold != threshold:                  # no positive anywhere: nothing to tune on
                 raise ValueError("evaluate_generation: the dataset has no edge to choose a threshold by")
         data, gen, pdata, pgen, mdata, mgen, sdata, sgen = [], [], [], [], [], [], [], []
+        xdata, xgen = [], []
         for i, b in enumerate(self.batches):
             data.append(self.model.graph_stats(b))
             if paths:
@@ -213,9 +222,12 @@ class Trainer:
                 mdata.append(self.model.graph_motifs(b))
             if spectrum:
                 sdata.append(self.model.graph_spectrum(b))
+            if crossings:
+                xdata.append(self.model.graph_crossings(b))
             out = self.model.generate(b if mode == "mean" else None, mode=mode, seed=seed, step=i,
                                       adj_format="csr", threshold=threshold, inclusive=inclusive, stats=True,
-                                      paths=paths, src_step=src_step, motifs=motifs, spectrum=spectrum)
+                                      paths=paths, src_step=src_step, motifs=motifs, spectrum=spectrum,
+                                      crossings=crossings)
             gen.append(out["generated_stats"])
             if paths:
                 pgen.append(out["generated_paths"])
@@ -223,6 +235,8 @@ class Trainer:
                 mgen.append(out["generated_motifs"])
             if spectrum:
                 sgen.append(out["generated_spectrum"])
+            if crossings:
+                xgen.append(out["generated_crossings"])
         data, gen = GraphStats.concat(data), GraphStats.concat(gen)
         if self.opt.distributed:
             data, gen = data.all_gather(self.opt.group), gen.all_gather(self.opt.group)
@@ -243,6 +257,11 @@ class Trainer:
             if self.opt.distributed:
                 sdata, sgen = sdata.all_gather(self.opt.group), sgen.all_gather(self.opt.group)
             out["spectrum"] = dict(sdata.compare(sgen), dataset=sdata, generated=sgen)
+        if crossings:
+            xdata, xgen = CrossingStats.concat(xdata), CrossingStats.concat(xgen)
+            if self.opt.distributed:
+                xdata, xgen = xdata.all_gather(self.opt.group), xgen.all_gather(self.opt.group)
+            out["crossings"] = dict(xdata.compare(xgen), dataset=xdata, generated=xgen)
         return out
 
     def save(self, path: str):
