@@ -1066,14 +1066,19 @@ int snd_generate(const snd_plan_t* plan, const snd_batch_t* batch, const float* 
  * "spmm_bf16" (the bf16 path's A @ dP1), "pack" / "dec:<k>" (bf16 weight
  * packing / k-th bf16 decoder kernel, k = 0..10), and on SND_TREF plans
  * "tref_head_fwd" / "tref_head_bwd" / "tref_proj_fwd" / "tref_proj_bwd"
- * (the weight-streaming heads and projection). */
+ * (the weight-streaming heads and projection), "wgrad_multi" (the last step's
+ * multi-segment weight-gradient launch) and "wgrad_multi:dims" (launches nothing:
+ * returns 3 when that launch carries (row chunk, pair group, segment) as its block
+ * indices, 1 when it takes the flattened grid). */
 int snd_plan_launch(const snd_plan_t* plan, const snd_batch_t* batch,
                     void* workspace, const char* kernel, snd_stream_t stream);
 /* Measurement only: bits that make the bf16 decoder kernels skip phases
  * (1 weight staging, 2 row staging, 4 MFMA, 8 stores, 16 column params,
  * 32 epilogue prefetch) and, read by snd_plan_create, 256 = generic-engine
  * plan, 512 = generic encoder; read by snd_train_step, 1024 = run the edge
- * terms and weight gradients on a side stream.  0 (default) = normal. */
+ * terms and weight gradients on a side stream, 4096 = one weight-gradient launch
+ * per weight, 1u << 31 = the multi-segment weight-gradient launch takes the flattened
+ * 1-D grid even when its segments are uniform.  0 (default) = normal. */
 int snd_debug_set(int flags);
 
 /* Plan options (round 4).  "conc_decoder": 1 = run the fused decoder on a side stream

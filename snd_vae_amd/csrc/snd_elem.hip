@@ -379,36 +379,75 @@ __host__ __device__ __forceinline__ int red_pl(int nparts, long long items) {
   return nparts >= 1024 ? 64
                         : (nparts >= 256 ? 32 : (nparts >= 64 ? (items >= kRedWide ? SND_RED_PL : 8) : (items >= kRedWide ? SND_RED_PLW : SND_RED_PLS)));
 }
-struct ReducePack {
-  ReduceDesc d[kMaxReduce];
-  int bstart[kMaxReduce + 1];   // first block of each descriptor (flattened 1-D grid)
+// a ReduceDesc and the first block of its range in the flattened grid: 16 dwords, 64-byte
+// aligned, so a block takes its whole descriptor in one 16-dword scalar load
+struct alignas(64) RedSeg {
+  const float* src;
+  float* dst;
+  int nparts;
+  int len;
+  long long stride;
+  float scale;
+  int accumulate;
+  int rows;
+  int b0;
+  long long src_rs, dst_rs;
 };
+static_assert(sizeof(RedSeg) == 64, "RedSeg: one 16-dword load");
+struct ReducePack {
+  RedSeg d[kMaxReduce];
+  int bstart[kMaxReduce + 1];   // first block of each descriptor (flattened 1-D grid); 64-byte aligned
+};
+static_assert(kMaxReduce == 48 && offsetof(ReducePack, bstart) % 64 == 0, "bstart is read as three 16-dword vectors");
+typedef int red_i16_t __attribute__((ext_vector_type(16)));
+
+#ifndef SND_RED_R0
+#define SND_RED_R0 8   // slab loads of a thread's first round (32, all of a 64-part PL = 2 slab's: C2's
+                       // reduce 9.40 us against 8.32 at 8, profiles/wgrad_reduce_args_ab.txt)
+#endif
 
 template <int NTF> __device__ void finalize_block(const FinalizeArgs& a);
 
 // fin: block 0 computes the loss terms (finalize) instead of a reduction block;
 // ADAM: descriptors of ra.mask (this launch's bits) also take their TF1 Adam update
+//
+// A block's chain: [bstart[] and the Adam arguments] -> [its descriptor] -> [the Adam
+// operands and the first round of slab loads] -> sums.  The step counter's load and the
+// f64 step-size arithmetic sit behind the issue of those loads and in front of their wait.
 template <bool FIN, bool ADAM>
 __global__ void __launch_bounds__(256) reduce_kernel(ReducePack pk, FinalizeArgs fin, ReduceAdam ra) {
   if constexpr (FIN) {
     if (blockIdx.x == 0) { finalize_block<256>(fin); return; }
   }
-  const int bid = (int)blockIdx.x - (FIN ? 1 : 0);
-  // descriptor of this block: the count of later starts <= bid (bstart is non-decreasing,
-  // unused entries hold the total): independent scalar loads, no dependent search chain
+  int bid = (int)blockIdx.x - (FIN ? 1 : 0);
+  // descriptor of this block: the last start <= bid (bstart is non-decreasing, unused
+  // entries hold the total).  One group of scalar loads -- the 48 starts as three vectors
+  // and the Adam arguments -- then scalar selects: no dependent search chain
+  const red_i16_t s0 = *reinterpret_cast<const red_i16_t*>(&pk.bstart[0]);
+  const red_i16_t s1 = *reinterpret_cast<const red_i16_t*>(&pk.bstart[16]);
+  const red_i16_t s2 = *reinterpret_cast<const red_i16_t*>(&pk.bstart[32]);
+  // (the empty asm statements tie a group's loads to one point, as in snd_head.hip; they
+  // are not volatile and name no memory, so the step counter's load below stays a scalar load)
+  if constexpr (ADAM)
+    asm("" : "+s"(bid) : "s"(s0), "s"(s1), "s"(s2), "s"(ra.mask), "s"(ra.gbase), "s"(ra.p), "s"(ra.m), "s"(ra.v),
+        "s"(ra.stepn));
+  else
+    asm("" : "+s"(bid) : "s"(s0), "s"(s1), "s"(s2));
   int di = 0;
 #pragma unroll
-  for (int i = 1; i < kMaxReduce; ++i) di += bid >= pk.bstart[i] ? 1 : 0;
+  for (int i = 1; i < kMaxReduce; ++i) di = bid >= (i < 16 ? s0[i] : (i < 32 ? s1[i - 16] : s2[i - 32])) ? i : di;
   di = __builtin_amdgcn_readfirstlane(di);
-  const ReduceDesc& d = pk.d[di];
-  const int bx = bid - pk.bstart[di];
-  // bias-corrected step size (snd_adam_tf1's arithmetic), while the slab loads are in flight
+  // the descriptor by value, in one piece (its first block rides in it)
+  // and the step counter (every block of an ADAM launch, a scalar load through the pointer
+  // of the first group): its trip is the descriptor's, not one more in the chain
+  const RedSeg d = pk.d[di];
+  int st = 0;
+  if constexpr (ADAM) st = *ra.stepn;
+  int b0 = d.b0;
+  asm("" : "+s"(b0) : "s"(d.src), "s"(d.dst), "s"(d.nparts), "s"(d.len), "s"(d.stride), "s"(d.scale),
+      "s"(d.accumulate), "s"(d.rows), "s"(d.src_rs), "s"(d.dst_rs), "s"(st));
+  const int bx = bid - b0;
   const bool dad = ADAM && ((ra.mask >> di) & 1ull);   // uniform per block
-  float lrt = 0.f;
-  if (dad) {
-    const int st = *ra.stepn;
-    lrt = (float)((double)ra.lr * sqrt(1.0 - pow((double)ra.b2, st)) / (1.0 - pow((double)ra.b1, st)));
-  }
   __shared__ double red[256];
   const int rows = d.rows > 0 ? d.rows : 1;
   const long long items = (long long)rows * d.len;
@@ -421,9 +460,20 @@ __global__ void __launch_bounds__(256) reduce_kernel(ReducePack pk, FinalizeArgs
   // the Adam operands (and an accumulated destination) do not depend on the sums: the
   // item's owner lane loads them before the slab loads, one round trip for both
   float pi = 0.f, mi = 0.f, vi = 0.f, prev = 0.f;
+  // the first round: up to SND_RED_R0 slab loads per thread (the 64-part weight slabs at 8
+  // part lanes: all of them), issued here and summed behind the step size below
+  constexpr int R0 = SND_RED_R0;
+  float v0[R0];
+#pragma unroll
+  for (int u = 0; u < R0; ++u) v0[u] = 0.f;
+  const float* src = d.src;
+  const bool ld0 = j < items && d.nparts > 0;
   if (j < items) {
-    r = (int)(j / d.len);
-    i = (int)(j - (long long)r * d.len);
+    // (one row, the usual slab: no division; under 2^31 items a 32-bit one -- the 64-bit
+    // division is some 200 instructions in front of the first load; same r and i)
+    if (rows == 1) { r = 0; i = (int)j; }
+    else if (items < (1ll << 31)) { r = (int)((unsigned)j / (unsigned)d.len); i = (int)((unsigned)j - (unsigned)r * (unsigned)d.len); }
+    else { r = (int)(j / d.len); i = (int)(j - (long long)r * d.len); }
     if (pl == 0) {
       const float* dst = d.dst + (long long)r * d.dst_rs + i;
       if (d.accumulate) prev = *dst;
@@ -434,12 +484,29 @@ __global__ void __launch_bounds__(256) reduce_kernel(ReducePack pk, FinalizeArgs
         }
       }
     }
-    const float* src = d.src + (long long)r * d.src_rs + i;
-    int p = pl;
-    // 8 loads in flight per round (the 64-part weight slabs at 8 part lanes: one round
-    // trip instead of two); the adds stay in part order
-    // (16 or 32 loads per round, i.e. 1-2 rounds per thread, measured no faster:
-    // profiles/r06_ab_reduce_rounds.txt)
+    src = d.src + (long long)r * d.src_rs + i;
+  }
+  if (ld0) {
+    // unconditional loads (a part past the end re-reads the last one and is not summed):
+    // no branch per load, nothing waits here
+#pragma unroll
+    for (int u = 0; u < R0; ++u) v0[u] = src[(long long)min(pl + u * PL, d.nparts - 1) * d.stride];
+  }
+  // the loads above are out; nothing below moves over this line, and they do not sink
+  // into the branches that consume them
+  asm volatile("" ::: "memory");
+  // bias-corrected step size (snd_adam_tf1's arithmetic): the f64 powers run while the
+  // operand and slab loads are in flight
+  float lrt = 0.f;
+  if (dad) lrt = (float)((double)ra.lr * sqrt(1.0 - pow((double)ra.b2, st)) / (1.0 - pow((double)ra.b1, st)));
+  asm volatile("" : "+v"(lrt) :: "memory");
+  if (j < items) {
+    // the adds stay in part order: the first round's, then rounds of 8, 4 and 1 as before
+#pragma unroll
+    for (int u = 0; u < R0; ++u)
+      if (pl + u * PL < d.nparts) acc += (double)v0[u];
+    int p = pl + R0 * PL;
+    // 8 loads in flight per round; the adds stay in part order
     for (; p + 7 * PL < d.nparts; p += 8 * PL) {
       float v[8];
 #pragma unroll
@@ -654,7 +721,9 @@ int launch_reduce(const ReduceDesc* d, int n, hipStream_t s, const FinalizeArgs*
     for (int i = 0; i < kMaxReduce; ++i) {
       pk.bstart[i] = (int)nb;
       if (i < cnt) {
-        pk.d[i] = d[base + i];
+        const ReduceDesc& x = d[base + i];
+        pk.d[i] = RedSeg{x.src, x.dst, x.nparts, x.len, x.stride, x.scale, x.accumulate, x.rows, (int)nb,
+                         x.src_rs, x.dst_rs};
         const long long items = (long long)(pk.d[i].rows > 0 ? pk.d[i].rows : 1) * pk.d[i].len;
         const int ipb = 256 / red_pl(pk.d[i].nparts, items);
         nb += (items + ipb - 1) / ipb;

@@ -505,7 +505,9 @@ __device__ __forceinline__ WgUnit wg_unit(const WgArgs& a, int sub, int s0, int 
   u.sub = sub; u.s0 = s0;
   if (a.T == 1) { u.glo = sub; u.ghi = send; u.s1 = send; }
   else {
-    const int gs = (s0 / a.npg) * a.npg;
+    // the graph of row s0 by the host's reciprocal (WgArgs::npg_m): no run-time division
+    const int g = a.npg_m ? (int)(((unsigned long long)(unsigned)s0 * a.npg_m) >> 32) : s0 / a.npg;
+    const int gs = g * a.npg;
     u.glo = gs; u.ghi = min(a.R, gs + a.npg); u.s1 = min(send, u.ghi);
   }
   return u;
@@ -563,19 +565,23 @@ __device__ __forceinline__ void wgrad_body(const WgArgs& a, const int bx, const 
   };
 
   // the first unit's DMA goes out before the pair bookkeeping below (round 5 stamps: the
-  // first unit's round trip was 3.7 us of a 12.8 us workgroup)
+  // first unit's round trip was 3.7 us of a 12.8 us workgroup); everything it reads is in
+  // the 16-dword header of WgArgs
   const WgUnit u0 = wg_unit(a, c0, c0, c1);
   if (c0 < c1) stage(u0, 0);
-  const int cbn = (a.K + 15) >> 4;
+  // cbn = cdiv(K, 16) and the pairs per workgroup come from the host (a.geo): no divide.
+  // p < P = T cbn with T <= 5, so p / cbn is a count of four compares
+  const int cbn = a.geo & 255, ppw = a.geo >> 8;
   const int P = T * cbn;
   bool pvs[NPW];
   int ts[NPW], cbs[NPW];
 #pragma unroll
   for (int i = 0; i < NPW; ++i) {
-    const int wl = w + 16 * i, p = by * a.pairs_per_wg + wl;
-    pvs[i] = wl < a.pairs_per_wg && p < P;
-    ts[i] = pvs[i] ? p / cbn : 0;
-    cbs[i] = pvs[i] ? p - ts[i] * cbn : 0;
+    const int wl = w + 16 * i, p = by * ppw + wl;
+    pvs[i] = wl < ppw && p < P;
+    const int t = (p >= cbn) + (p >= 2 * cbn) + (p >= 3 * cbn) + (p >= 4 * cbn);
+    ts[i] = pvs[i] ? t : 0;
+    cbs[i] = pvs[i] ? p - t * cbn : 0;
   }
   const bool pv = pvs[0];
 
@@ -668,17 +674,27 @@ __global__ void __launch_bounds__(WGT) wgrad_kernel(WgArgs a) {
 // (row chunk, pair group) geometry.  Segments are independent (they read
 // finished dy's and write their own slabs), so one launch replaces one dependent
 // launch per weight.
-struct WgMultiPack {
-  WgArgs a[kMaxWgMulti];
-  int start[kMaxWgMulti + 1];
+struct alignas(64) WgMultiPack {
+  int start[kMaxWgMulti + 1];   // in front, 64-byte aligned: the flattened grid fetches it as two 16-dword loads
   int nseg;
   int stamp_base;   // measurement only: workgroups of the earlier launches of the same call
+  WgArgs a[kMaxWgMulti];
 };
 static_assert(sizeof(WgMultiPack) <= 4096, "wgrad_multi: kernel arguments over 4 KB");
 
 // Every segment is at most 64 columns of dy wide (launch_wgrad_multi splits wider ones)
 // and its staging at most 68 KB: the kernel is built for 8 waves per SIMD (<= 64 VGPRs),
 // two workgroups per CU.
+// G3: every segment has the same (row chunks, pair groups) grid, and the launch carries
+// (row chunk, pair group, segment) as its three block indices: a workgroup's only
+// kernel-argument trip before its first DMA is its segment's 16-dword header.  Otherwise
+// the grid is flattened: the segment is a count over start[] (one group of loads), and the
+// header and the segment's first workgroup follow in a second.  No path reads the grid
+// size or divides by a run-time value (gx comes from the host; by = local / gx is a
+// compare chain: a segment has at most 5 * 8 pairs, so at most 3 pair groups of >= 16).
+typedef int wg_hdr_t __attribute__((ext_vector_type(16), aligned(8)));
+typedef int wg_i16_t __attribute__((ext_vector_type(16)));
+template <bool G3>
 __global__ void __launch_bounds__(WGT) __attribute__((amdgpu_waves_per_eu(8, 8)))
 wgrad_multi_kernel(WgMultiPack m) {
   extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
@@ -686,24 +702,45 @@ wgrad_multi_kernel(WgMultiPack m) {
   const bool stamp = (kdbg(m.a[0].dbg) & (1 << 21)) && m.a[0].stamps;
   wg_stamp(tsl, 0, stamp);
   if (kdbg(m.a[0].dbg) & 1) return;   // measurement only: the launch alone
-  // segment of this block: independent scalar loads of the starts (entries past nseg hold
-  // the grid size), no dependent search chain
-  // (a 2-D grid when every segment has the same item count: the segment is blockIdx.y,
-  // and its arguments are the workgroup's first kernel-argument loads)
-  const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-  int s = 0;
-  if (gridDim.y > 1) {
-    s = blockIdx.y;
+  int s = 0, first = 0;   // the segment, and its first workgroup in the flattened grid
+  if constexpr (G3) {
+    s = blockIdx.z;
   } else {
+    // the starts in one group of scalar loads (entries past nseg hold the grid size), then
+    // scalar selects: no dependent search chain
+    static_assert(kMaxWgMulti == 32, "start[] is read as two 16-dword vectors");
+    const wg_i16_t lo = *reinterpret_cast<const wg_i16_t*>(&m.start[0]);
+    const wg_i16_t hi = *reinterpret_cast<const wg_i16_t*>(&m.start[16]);
+    asm volatile("" :: "s"(lo), "s"(hi));   // both before the first compare: one wait
+    // (the starts do not decrease: the last one at or below the block is the segment's own,
+    // taken from the registers, not by a dependent load of start[s])
 #pragma unroll
-    for (int i = 1; i < kMaxWgMulti; ++i) s += (int)blockIdx.x >= m.start[i] ? 1 : 0;
+    for (int i = 1; i < kMaxWgMulti; ++i) {
+      const int st = i < 16 ? lo[i] : hi[i - 16];
+      const bool in = (int)blockIdx.x >= st;
+      s = in ? i : s;
+      first = in ? st : first;
+    }
+    s = __builtin_amdgcn_readfirstlane(s);
+    first = __builtin_amdgcn_readfirstlane(first);
   }
-  s = __builtin_amdgcn_readfirstlane(s);
-  const WgArgs a = m.a[s];   // by value: field reads stay scalar loads from the kernarg segment
-  const int local = gridDim.y > 1 ? (int)blockIdx.x : (int)blockIdx.x - m.start[s];
-  const int gx = cdiv_d(a.R, a.rows_per_wg);
-  const int bx = local % gx, by = local / gx;
-  const bool two = a.pairs_per_wg > WGT / 64;
+  // by value: field reads stay scalar loads from the kernarg segment.  The header goes
+  // through one 16-dword vector so that it is one load, not one per use.
+  WgArgs a = m.a[s];
+  const wg_hdr_t hdr = *reinterpret_cast<const wg_hdr_t*>(&m.a[s]);
+  __builtin_memcpy(&a, &hdr, sizeof(hdr));
+  // the epilogue's six dwords ride in the same trip: left to the compiler they are fetched
+  // behind the header's wait, a second trip in front of the first DMA
+  asm volatile("" :: "s"(a.slab), "s"(a.sK), "s"(a.sn4), "s"(a.wk0), "s"(a.wn0), "s"(a.geo));
+  int bx, by;
+  if constexpr (G3) {
+    bx = blockIdx.x; by = blockIdx.y;
+  } else {
+    const int local = (int)blockIdx.x - first;
+    by = (local >= a.gx) + (local >= 2 * a.gx);
+    bx = local - by * a.gx;
+  }
+  const bool two = (a.geo >> 8) > WGT / 64;
   if (kdbg(a.dbg) & 16) return;   // measurement only: launch + segment lookup
   unsigned* ts = stamp ? tsl : nullptr;
   wg_stamp(ts, 1, stamp);
@@ -716,6 +753,8 @@ wgrad_multi_kernel(WgMultiPack m) {
   if (stamp) {
     __syncthreads();
     if (threadIdx.x == 0) {
+      // the workgroup's index in the flattened (segment, pair group, row chunk) order
+      const int bid = (G3 ? m.start[s] : first) + by * a.gx + bx;
       unsigned* o = m.a[0].stamps + ((long long)m.stamp_base + bid) * kWgStampWords;
       for (int i = 0; i < 9; ++i) o[i] = tsl[i];
       o[9] = (unsigned)__builtin_amdgcn_s_memrealtime();
@@ -998,9 +1037,18 @@ int launch_rowconv(const RcArgs& a0, int epi, hipStream_t s) {
 }
 
 // a descriptor's own slab geometry (sK, sn4 = 0: the whole weight at origin 0)
+// the host-computed quotients of a descriptor's header (after any change of K or pairs_per_wg)
+static void wg_quotients(WgArgs& x) {
+  x.gx = x.rows_per_wg > 0 ? cdiv(x.R, x.rows_per_wg) : 0;
+  x.geo = cdiv(x.K, 16) | (x.pairs_per_wg << 8);
+  // with e = npg_m * npg - 2^32 in (0, npg]: r * npg_m / 2^32 = r / npg + r e / (npg 2^32), and
+  // the second term stays under 1 / npg, the smallest gap to the next integer, while r e < 2^32
+  x.npg_m = (x.npg >= 2 && (long long)x.R * x.npg < (1ll << 32)) ? (unsigned)((1ull << 32) / (unsigned)x.npg) + 1u : 0u;
+}
 static WgArgs wg_norm(const WgArgs& a) {
   WgArgs x = a;
   if (x.sK == 0) { x.sK = x.K; x.sn4 = wgrad_n4(x.N); x.wk0 = 0; x.wn0 = 0; }
+  wg_quotients(x);
   return x;
 }
 
@@ -1027,25 +1075,36 @@ static int wg_split(const WgArgs& a, WgArgs* out, int cap) {
       w.dy = static_cast<const __bf16*>(a.dy) + n0;
       w.wk0 = a.wk0 + k0; w.wn0 = a.wn0 + n0;
       w.pairs_per_wg = std::min(a.pairs_per_wg, a.T * cdiv(w.K, 16));
+      wg_quotients(w);
       out[n++] = w;
     }
   return n;
 }
 
-static int wg_multi_flush(WgMultiPack& pk, int total, size_t lds, hipStream_t s) {
+// the (row chunks, pair groups) grid of a segment
+static int wg_gy(const WgArgs& x) { return cdiv(x.T * cdiv(x.K, 16), x.pairs_per_wg); }
+
+// dims != nullptr: no launch, the number of block indices the launch would use
+static int wg_multi_flush(WgMultiPack& pk, int total, size_t lds, hipStream_t s, int* dims) {
   if (pk.nseg == 0) return 0;
   for (int i = pk.nseg; i <= kMaxWgMulti; ++i) pk.start[i] = total;
-  bool uniform = pk.nseg > 1;
-  for (int i = 1; i < pk.nseg; ++i) uniform = uniform && pk.start[i + 1] - pk.start[i] == pk.start[1];
-  const dim3 grid = uniform ? dim3(pk.start[1], pk.nseg) : dim3(total);
-  hipLaunchKernelGGL(wgrad_multi_kernel, grid, dim3(WGT), lds, s, pk);
+  // every segment the same grid (C2: 64 row chunks x 1 pair group): the block indices are
+  // (row chunk, pair group, segment).  Host debug bit 1 << 31 forces the flattened grid
+  // (A/B, and the test that runs both paths on one shape)
+  const int gx = pk.a[0].gx, gy = wg_gy(pk.a[0]);
+  bool uniform = pk.nseg > 1 && !((unsigned)debug_flags() & (1u << 31));
+  for (int i = 1; i < pk.nseg; ++i) uniform = uniform && pk.a[i].gx == gx && wg_gy(pk.a[i]) == gy;
+  if (dims) { *dims = std::min(*dims, uniform ? 3 : 1); return 0; }
+  if (uniform) hipLaunchKernelGGL(wgrad_multi_kernel<true>, dim3(gx, gy, pk.nseg), dim3(WGT), lds, s, pk);
+  else hipLaunchKernelGGL(wgrad_multi_kernel<false>, dim3(total), dim3(WGT), lds, s, pk);
   SND_LAUNCH_CHECK("wgrad_multi_kernel");
   return 0;
 }
 
 // one launch per kMaxWgMulti segments (C2: 13 segments after the window split, one launch)
-int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s) {
+int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s, int* dims) {
   if (n <= 0) return 0;
+  if (dims) *dims = 3;
   WgMultiPack pk{};
   size_t lds = 0;
   int total = 0, base = 0;
@@ -1058,7 +1117,8 @@ int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s) {
     SND_CHECK_ARG(x0.K > 0 && x0.K <= 128 && x0.N > 0 && x0.N <= 128, "wgrad_multi: K %d N %d", x0.K, x0.N);
     SND_CHECK_ARG(x0.ldx % 8 == 0 && x0.lddy % 8 == 0 && x0.x_bf16 && x0.dy_bf16,
                   "wgrad_multi: bf16 operands with leading dims %% 8");
-    SND_CHECK_ARG(x0.rows_per_wg % kRcRows == 0 && x0.pairs_per_wg >= 1 && x0.pairs_per_wg <= 2 * WGT / 64,
+    SND_CHECK_ARG(x0.rows_per_wg % kRcRows == 0 && x0.rows_per_wg > 0 && x0.pairs_per_wg >= 1 &&
+                      x0.pairs_per_wg <= 2 * WGT / 64,
                   "wgrad_multi: geometry");
     SND_CHECK_ARG(x0.x && x0.dy && x0.slab && x0.zero && x0.npg > 0, "wgrad_multi: null operand");
     SND_CHECK_ARG(x0.sn4 % 4 == 0 && x0.wn0 % 4 == 0 && x0.wk0 + x0.K <= x0.sK &&
@@ -1068,7 +1128,7 @@ int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s) {
     SND_CHECK_ARG(nw > 0, "wgrad_multi: window split");
     for (int j = 0; j < nw; ++j) {
       if (pk.nseg == kMaxWgMulti) {   // pack full: launch it, start the next
-        SND_TRY(wg_multi_flush(pk, total, lds, s));
+        SND_TRY(wg_multi_flush(pk, total, lds, s, dims));
         base += total;
         pk = WgMultiPack{};
         pk.stamp_base = base;
@@ -1076,10 +1136,11 @@ int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s) {
         total = 0;
       }
       const WgArgs& x = win[j];
-      const int P = x.T * cdiv(x.K, 16);
+      // the flattened grid's pair group is a two-compare chain
+      SND_CHECK_ARG(wg_gy(x) <= 3, "wgrad_multi: %d pair groups", wg_gy(x));
       pk.a[pk.nseg] = x;
       pk.start[pk.nseg] = total;
-      total += cdiv(x.R, x.rows_per_wg) * cdiv(P, x.pairs_per_wg);
+      total += x.gx * wg_gy(x);
       lds = std::max(lds, wg_lds_bytes(x.T, x.K, x.N));
       ++pk.nseg;
       SND_CHECK_ARG(!stamps || ((long long)base + total) * kWgStampWords <= a[0].stamp_words,
@@ -1087,7 +1148,7 @@ int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s) {
                     a[0].stamp_words);
     }
   }
-  return wg_multi_flush(pk, total, lds, s);
+  return wg_multi_flush(pk, total, lds, s, dims);
 }
 
 WgGeom wgrad_geom(int R, int T, int K, int N, int chunks) {
@@ -1111,8 +1172,12 @@ WgGeom wgrad_geom(int R, int T, int K, int N, int chunks) {
 }
 
 int launch_wgrad(const WgArgs& a0, hipStream_t s) {
-  const WgArgs a = wg_norm(a0);
+  WgArgs a = wg_norm(a0);
   if (a.R <= 0) return 0;
+  // a descriptor with the multi-segment geometry (up to 32 pairs, two per wave): this
+  // kernel takes one pair per wave, so the same pairs spread over more pair groups.  A
+  // pair's slab block does not depend on the workgroup that computes it: the same bits
+  if (a.pairs_per_wg > WGT / 64) { a.pairs_per_wg = WGT / 64; wg_quotients(a); }
   SND_CHECK_ARG(a.T == 1 || a.T == 5, "wgrad: T must be 1 or 5");
   SND_CHECK_ARG(a.K > 0 && a.K <= 128 && a.N > 0 && a.N <= 128, "wgrad: K %d N %d", a.K, a.N);
   SND_CHECK_ARG(a.ldx % 8 == 0 && a.lddy % 8 == 0 && a.x_bf16 && a.dy_bf16,
@@ -1153,7 +1218,9 @@ static int fast_init_attributes_once() {
   SND_ATTR((wgrad_kernel<4>)) SND_ATTR((wgrad_kernel<5>)) SND_ATTR((wgrad_kernel<6>))
   SND_ATTR((wgrad_kernel<7>)) SND_ATTR((wgrad_kernel<8>))
 #undef SND_ATTR
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_multi_kernel),
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_multi_kernel<true>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgMultiLds) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_multi_kernel<false>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgMultiLds) != hipSuccess) {
     set_error("hipFuncSetAttribute(wgrad_multi_kernel) failed");
     return SND_ERR_HIP;

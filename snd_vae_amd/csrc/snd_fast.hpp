@@ -3,6 +3,7 @@
 // weight-gradient engine (LDS transpose reads).  The f32 parity mode keeps
 // the generic GEMM engine of snd_gemm.hip.
 #pragma once
+#include <cstddef>
 #include "snd_common.hpp"
 
 namespace snd {
@@ -101,21 +102,34 @@ int launch_rowconv(const RcArgs& a, int epi, hipStream_t s);
 // (same per-graph zero padding), k < K, n < N; slab rows are padded to
 // n4 = round_up(N, 4) floats (wgrad_n4).  Deterministic partials.
 struct WgArgs {
-  const void* x; int ldx; int K; int x_bf16;
-  const void* dy; int lddy; int N; int dy_bf16;
-  int R, npg, T;
-  int rows_per_wg;              // multiple of kRcRows
-  int pairs_per_wg;             // (tap, 16-column k block) pairs per workgroup (<= 20)
-  float* slab;
+  // The first 16 dwords are everything a workgroup needs before its first unit's LDS-DMA
+  // (wg_unit, stage and the kernel's dispatch): the multi-segment kernel takes them in one
+  // 16-dword scalar load, one trip to the kernel-argument segment.
+  const void* x; const void* dy;
   const void* zero;             // >= 16 zero bytes in device memory
-  int dbg;
+  int R, ldx, lddy, K, N, T, npg;
+  int rows_per_wg;              // multiple of kRcRows
+  // set by the launchers (wg_norm), not by the caller: quotients of the fields above, so
+  // that no workgroup divides.  geo = cdiv(K, 16) | pairs_per_wg << 8;
+  // npg_m = floor(2^32 / npg) + 1: (r * npg_m) >> 32 == r / npg for every row r < R when
+  // R * npg < 2^32 (0 otherwise, and for npg < 2: the kernel divides)
+  int geo;
+  unsigned npg_m;
+  // ---- the epilogue's fields, 6 dwords fetched in the same trip
+  float* slab;
   // slab geometry of the whole weight when this descriptor is a (k, n) window of it
   // (launch_wgrad_multi's LDS split): rows sK, padded width sn4, window origin
   // (wk0, wn0); 0 = the descriptor's own K / n4(N) at origin 0
   int sK, sn4, wk0, wn0;
+  int gx;                       // set by the launchers: cdiv(R, rows_per_wg) row chunks (the flattened grid reads it)
+  // ---- host side, and measurement
+  int pairs_per_wg;             // (tap, 16-column k block) pairs per workgroup (<= 32)
+  int dbg;
+  short x_bf16, dy_bf16;        // (shorts: 32 descriptors and the segment starts fit 4 KB of kernel arguments)
   unsigned* stamps;             // measurement only (debug bit 1 << 21): 12 words per workgroup
   long long stamp_words;        // capacity of stamps in words (checked by launch_wgrad_multi)
 };
+static_assert(offsetof(WgArgs, slab) == 64 && sizeof(WgArgs) == 120, "WgArgs: the 16-dword header; 120 bytes");
 struct WgGeom { int rows_per_wg, pairs_per_wg, gx, gy; };
 // chunks > 0: that many row chunks per weight (the step's multi-segment launch);
 // 0: about 256 workgroups per weight (one launch each)
@@ -124,7 +138,9 @@ inline int wgrad_n4(int N) { return (N + 3) & ~3; }
 int launch_wgrad(const WgArgs& a, hipStream_t s);
 // n independent weight gradients (each its own geometry and slab) in one launch
 constexpr int kMaxWgMulti = 32;   // segments after the column-window split (C5: 29)
-int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s);
+// dims != nullptr: nothing is launched; *dims = 3 when every launch of the call would carry
+// (row chunk, pair group, segment) as its block indices, 1 when any takes the flattened grid
+int launch_wgrad_multi(const WgArgs* a, int n, hipStream_t s, int* dims = nullptr);
 
 // ---- fused sigmoid head + MSE + backward + BN/lrelu backward of the head's
 // input layer (model_joint.py:115-121,138-144; optimizer.py:149,153).

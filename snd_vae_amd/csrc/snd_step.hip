@@ -1563,7 +1563,10 @@ extern "C" int snd_plan_launch(const snd_plan_t* plan, const snd_batch_t* batch,
       return launch_tref_proj_bwd(a, s);
     }
   }
-  if (!strcmp(kernel, "wgrad_multi")) {   // the last step's weight gradients (current debug bits)
+  // the last step's weight gradients (current debug bits); ":dims" launches nothing and
+  // returns the number of block indices the launch carries (3 or 1)
+  const bool wg_dims = !strcmp(kernel, "wgrad_multi:dims");
+  if (wg_dims || !strcmp(kernel, "wgrad_multi")) {
     SND_CHECK_ARG(!p.last_wq.empty(), "snd_plan_launch: no multi-segment weight-gradient launch yet");
     std::vector<WgArgs> q = p.last_wq;
     for (auto& w : q) {
@@ -1574,6 +1577,11 @@ extern "C" int snd_plan_launch(const snd_plan_t* plan, const snd_batch_t* batch,
       const bool st = (w.dbg & (1 << 21)) && p.dec_fused;
       w.stamps = st ? reinterpret_cast<unsigned*>(ws + p.buf("PDHS")) : nullptr;
       w.stamp_words = st ? p.buf_numel("PDHS") : 0;
+    }
+    if (wg_dims) {
+      int dims = 0;
+      SND_TRY(launch_wgrad_multi(q.data(), (int)q.size(), s, &dims));
+      return dims;
     }
     return launch_wgrad_multi(q.data(), (int)q.size(), s);
   }

@@ -11,6 +11,20 @@ the last one only lowers the count on the same group: no new round trip).  A wai
 loads is a memory round trip that hides almost nothing behind it; a kernel whose
 time is one tile's dependent chain pays each of them in full.  Only loads, waits and
 barriers are read: the counts say nothing about what the loads fetch.
+
+    python tools/load_chains.py --args --kernels 'wgrad|reduce_kernel'
+
+--args adds a second count per kernel, the scalar chain in front of the first vector-memory
+instruction (load, store, atomic or LDS-DMA): the `s_waitcnt` carrying `lgkmcnt` that follow
+at least one `s_load*` / `s_buffer_load*` issued since the previous such wait, and the
+number of instructions up to that first vector-memory instruction.  Each such wait is one
+dependent round trip to the kernel-argument segment (or to memory through a pointer taken
+from it) that every workgroup pays before its first useful load.  The count is over the
+program text, not over an execution: it includes the paths a given launch does not take
+(both sides of a branch laid out before the first vector-memory instruction count), and
+it stops at the first vector-memory instruction in text order even where a launch
+branches round it.  With --args the kernel's VGPRs, SGPRs and `v_writelane` count (SGPR
+spills into VGPR lanes) are printed when the input has them (hipcc -S files).
 """
 import argparse
 import os
@@ -27,6 +41,8 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 DEFAULT = r"enc_front_kernel<2>|head_fwd_kernel<64, 2, 4>|head_bwd_kernel<128, 1, 2, 3>"
 
 LOAD = re.compile(r"^(global_load|buffer_load|flat_load|scratch_load)")   # LDS-DMA forms included
+VMEM = re.compile(r"^(global_|buffer_|flat_|scratch_)(load|store|atomic)")
+SLOAD = re.compile(r"^s_(buffer_)?load")
 LABEL_S = re.compile(r"^(_Z\w+):")                       # hipcc -S
 LABEL_D = re.compile(r"^[0-9a-f]+ <(_Z\w+)>:")           # llvm-objdump -d
 
@@ -99,6 +115,64 @@ def chains(insts):
     return r
 
 
+def arg_waits(insts):
+    """The scalar chain in front of the first vector-memory instruction, in program order:
+    waits on scalar loads (an lgkmcnt wait with at least one scalar load since the previous
+    one), the scalar loads, and the instructions up to that vector-memory instruction; over
+    the whole kernel, the v_writelane count.  Program text: untaken paths count too."""
+    r = {"arg_waits": 0, "arg_loads": 0, "insts_to_vmem": 0, "writelanes": 0}
+    since, front = 0, True
+    for s in insts:
+        if s.startswith("v_writelane"):
+            r["writelanes"] += 1
+        if not front:
+            continue
+        if VMEM.match(s):
+            front = False
+            continue
+        r["insts_to_vmem"] += 1
+        if SLOAD.match(s):
+            since += 1
+            r["arg_loads"] += 1
+        elif s.startswith("s_waitcnt") and "lgkmcnt(" in s and since:
+            r["arg_waits"] += 1
+            since = 0
+    return r
+
+
+def registers(text):
+    """{mangled name: (vgprs, sgprs)} from the .amdhsa directives of a hipcc -S file."""
+    out, v = {}, {}
+    for line in text.splitlines():
+        m = re.match(r"\s*\.amdhsa_kernel (\S+)", line)
+        if m:
+            v = out.setdefault(m.group(1), {})
+        m = re.match(r"\s*\.amdhsa_next_free_([vs])gpr (\d+)", line)
+        if m:
+            v[m.group(1)] = int(m.group(2))
+    return out
+
+
+def report_args(text, pattern):
+    regs = registers(text)
+    rows = {}
+    for m, insts in kernels(text).items():
+        name = short_name(m)
+        if re.search(pattern, name):
+            rows[name] = dict(arg_waits(insts), vgprs=regs.get(m, {}).get("v"), sgprs=regs.get(m, {}).get("s"))
+    return rows
+
+
+def format_args(rows):
+    out = [f"{'kernel':44s} {'arg waits':>9s} {'s_loads':>7s} {'insts to vmem':>13s} | {'VGPRs':>5s} {'SGPRs':>5s} {'v_writelane':>11s}"]
+    for name in sorted(rows):
+        r = rows[name]
+        reg = lambda k: f"{r[k]:5d}" if r.get(k) is not None else "    -"
+        out.append(f"{name:44s} {r['arg_waits']:9d} {r['arg_loads']:7d} {r['insts_to_vmem']:13d} | "
+                   f"{reg('vgprs')} {reg('sgprs')} {r['writelanes']:11d}")
+    return "\n".join(out)
+
+
 def short_name(mangled):
     """_ZN3snd12_GLOBAL__N_116enc_front_kernelILi2EEEvNS_9FrontArgsE -> enc_front_kernel<2>
     (nested names and integer template arguments: all this library's kernels have)"""
@@ -141,6 +215,8 @@ def main():
     ap.add_argument("files", nargs="*", help="hipcc -S outputs (default: disassemble --lib)")
     ap.add_argument("--lib", default=os.path.join(ROOT, "snd_vae_amd", "libsndvae.so"))
     ap.add_argument("--kernels", default=DEFAULT, help="regex on the kernel's short name, e.g. 'head_fwd_kernel<64, 2, 4>'")
+    ap.add_argument("--args", action="store_true",
+                    help="also the scalar-load waits in front of the first vector-memory instruction")
     args = ap.parse_args()
     if args.files:
         text = "\n".join(open(f).read() for f in args.files)
@@ -150,6 +226,9 @@ def main():
     if not rows:
         sys.exit(f"no kernel matches {args.kernels!r}")
     print(format_rows(rows))
+    if args.args:
+        print()
+        print(format_args(report_args(text, args.kernels)))
 
 
 if __name__ == "__main__":
