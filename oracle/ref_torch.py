@@ -7,7 +7,8 @@ own (dense, materialising) formulation on purpose:
 * ``tf.matmul(adj, X @ w)`` with the dense [B,N,N] adjacency (`layers.py:120-123`)
 * logits materialised as [B,N,N,2] with the numpy ``diag`` constant
   (`model.py:185,205-207`), softmax-CE against ``concat([1-A, A])``
-  (`optimizer.py:142-144`)
+  (`optimizer.py:142-144`); at pos_weight / norm other than 1 the weighted BCE on the
+  pair's logit, written independently of ``ref_numpy``
 * ``tf.layers.conv1d`` SAME as F.conv1d(padding=2) (`model_joint.py:115,138`)
 * TF1 Adam (`optimizer.py:125,197`)
 
@@ -85,8 +86,16 @@ def decoder_losses(p, J, adj, Xf, S, mu, s, cfg):
     l1 = diag * logit                                      # model.py:205
     logits = torch.stack([l0, l1], -1)
     labels = torch.stack([1 - adj, adj], -1)               # optimizer.py:142
-    ce = -(labels * torch.log_softmax(logits, -1)).sum(-1)
-    adj_cost = ce.mean()
+    if cfg.pos_weight == 1.0 and cfg.norm == 1.0:
+        ce = -(labels * torch.log_softmax(logits, -1)).sum(-1)
+        adj_cost = ce.mean()
+    else:
+        # tf.nn.weighted_cross_entropy_with_logits on the pair's logit
+        # x = l1 - l0 (the logit off the diagonal, -1 on it: softplus(-1) there as above),
+        # norm * mean(pos_weight * A * softplus(-x) + (1 - A) * softplus(x))
+        x = l1 - l0
+        pw = torch.tensor(float(cfg.pos_weight), dtype=X.dtype)
+        adj_cost = float(cfg.norm) * F.binary_cross_entropy_with_logits(x, adj, pos_weight=pw)
     generated_adj = torch.argmax(torch.softmax(logits, -1), -1)
     acc = (generated_adj == adj.long()).double().mean()
 

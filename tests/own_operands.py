@@ -23,6 +23,9 @@ Bounds, all derived (none comes from a GPU measurement):
 * a link through exp / sigmoid adds 1e-6 relative of the transcendental's value (v_exp_f32,
   v_rcp_f32: 1 ulp each, plus the argument's scaling to base 2), as
   ``parity_bars.own_structure`` already allows;
+* the per-edge coefficient (pw - 1) sigmoid(L) - pw of the weighted CE adds, per edge,
+  |pw - 1| (sigmoid' dL + 1e-6 sigmoid) |z_j| with dL the fp32 bound of the d-term logit
+  (tests/zzt_ops.py derives the stand-alone op's the same way); exactly zero at pw = 1;
 * a sum of values that an upstream link could not pin exactly (an intermediate the plan
   does not materialise, kink elements) carries that upstream bound, propagated.
 
@@ -156,6 +159,32 @@ def conv_wgrad(x, dy, n):
 
 def sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
+
+
+def edge_sigmoid(x):
+    """sigmoid(x) as edge_ce_terms (snd_common.hpp) orders it, in x's dtype: e = e^-|x|,
+    r = 1 / (1 + e), r for x >= 0 and e r below."""
+    e = np.exp(-np.abs(x))
+    r = 1 / (1 + e)
+    return np.where(x >= 0, r, e * r)
+
+
+def edge_coef(x, pw):
+    """The per-edge gradient coefficient of an A = 1 pair with logit x on top of the dense
+    kernel's sigmoid(x): -pw + (pw - 1) sigmoid(x); -pw alone at pw == 1 (the early-out)."""
+    coef = np.full(x.shape, -pw, x.dtype)
+    if pw != 1:
+        coef = coef + (pw - 1) * edge_sigmoid(x)
+    return coef
+
+
+def loss_scales(cfg, B, n, RH, L, k32):
+    """(pos_weight, adj_scale, kl_scale) as the step forms them (snd_step.hip): the config
+    holds pos_weight / norm / beta as floats (``k32``), adj_scale = 2 norm / (B n^2) and
+    kl_scale = beta / (RH L) are evaluated in double and passed to the kernels as floats."""
+    adj = k32(2.0 * float(k32(cfg.norm)) / (float(B) * n * n))
+    klc = k32(float(k32(cfg.beta)) / (float(RH) * L))
+    return k32(cfg.pos_weight), adj, klc
 
 
 def zzt_dp(d):
@@ -485,28 +514,49 @@ def step_links(b: Dict[str, np.ndarray], p, batch, cfg, plan: Plan, dt=np.float6
     yield "g:dec.Wn", g2n["W"]
     yield "g:dec.bn", g2n["b"]
 
-    # ================= dJ -> d[mu | s] (edge terms at pos_weight 1: coef = -1, e_i = -sum_j z_j)
-    assert cfg.pos_weight == 1.0 and cfg.norm == 1.0
-    k32 = (lambda v: v) if plan.compose else np.float32       # the step passes both as float
-    adj = dt(k32(2.0 * cfg.norm / (float(B) * n * n)))
+    # ================= dJ -> d[mu | s]
+    # The per-edge terms (edge_ce_terms: head_bwd_kernel, the d = 128 edge + reparam kernel,
+    # edge_bf16_kernel), never materialised on the fused paths: L_ij = ZB_i . ZB_j over the
+    # stored bf16 z (fp32 sum of d exact products), coef_ij = (pw - 1) sigmoid(L_ij) - pw on
+    # top of the dense kernel's sigmoid, e_i = sum_j coef_ij ZB_j over the row's neighbours.
+    # The coefficient's own error (the fp32 logit through sigmoid', 1e-6 of the sigmoid for
+    # exp / rcp and the two roundings that form coef) times |ZB_j| is the extra; at pw == 1
+    # the coefficient is -1, its error exactly zero and e_i = -sum_j z_j.
+    k32 = (lambda v: v) if plan.compose else np.float32       # the step passes them as floats
     RH = B if plan.tref else R
-    klc = dt(k32(cfg.beta / (float(RH) * L)))
-    EJ, EJm = -(A @ ZB), A @ ab(ZB)
+    pw, adj, klc = (dt(v) for v in loss_scales(cfg, B, n, RH, L, k32))
+    ei = np.repeat(np.arange(R), np.diff(batch.rowptr))
+    ej_ = batch.colidx.astype(np.int64)
+    Le = (ZB[ei] * ZB[ej_]).sum(1)
+    coef = edge_coef(Le, pw)
+    if pw != 1:
+        L64, pw64 = np.asarray(Le, f64), float(pw)
+        dLe = (dj + 4) * U23 * (np.abs(ZB[ei]).astype(f64) * np.abs(ZB[ej_]).astype(f64)).sum(1)
+        sg = sigmoid(L64)
+        dcoef = abs(pw64 - 1.0) * (sg * (1 - sg) * dLe + TRANS * sg)
+    else:
+        dcoef = np.zeros(len(ei))
+    rp, ci = batch.rowptr.astype(np.int64), batch.colidx.astype(np.int64)
+    import scipy.sparse as sp
+    C = sp.csr_matrix((coef, ci, rp), shape=(R, R))
+    EJ, EJm = C @ ZB, abs(C) @ ab(ZB)
+    EJx = float(abs(adj)) * (sp.csr_matrix((dcoef, ci, rp), shape=(R, R)) @ np.abs(ZB).astype(f64))
 
-    def reparam_bwd(dz, dzm, Kz, stored):
-        """reparam_bwd_elem: dm = kl mu + dz; dl = dz eps e^s + kl (e^2s - 1)."""
+    def reparam_bwd(dz, dzm, Kz, stored, dzx=0.0):
+        """reparam_bwd_elem: dm = kl mu + dz; dl = dz eps e^s + kl (e^2s - 1); ``dzx``: an
+        absolute allowance on dz, carried into both halves."""
         dm, dmm = klc * mu + dz, ab(klc * mu) + dzm
         dl = dz * EPS * es + klc * (es * es - 1)
         dlm = dzm * ab(EPS * es) + ab(klc) * (es * es + 1)
         ext = TRANS * np.asarray(ab(dz * EPS * es) + 2 * ab(klc) * es * es, f64)
         return Link(np.concatenate([dm, dl], 1), np.concatenate([dmm, dlm], 1), Kz + 4, stored,
-                    extra=np.concatenate([np.zeros(dm.shape), ext], 1))
+                    extra=np.concatenate([np.zeros(dm.shape) + dzx, ext + dzx * np.asarray(ab(EPS * es), f64)], 1))
 
     if not plan.tref:
         dz = adj * (DJD + EJ) + DZDEC
         # (the kernel adds the zz^T column-split partials in fp32 first: their |.| sum if given)
         dzm = ab(adj) * (T(b.get("DJD_abs", ab(DJD))) + EJm) + ab(DZDEC)
-        dms = reparam_bwd(dz, dzm, deg + 4, "bf16")
+        dms = reparam_bwd(dz, dzm, deg + 4, "bf16", EJx)
         yield "FDMS", dms
         DMS = T(b["FDMS"])
         # the [mu | s] bias gradient: column sums of the fp32 values before the bf16 rounding
@@ -525,10 +575,11 @@ def step_links(b: Dict[str, np.ndarray], p, batch, cfg, plan: Plan, dt=np.float6
         dJ = (adj * (DJD + EJ) + DZDEC).reshape(B, n * dj)
         dJm = (ab(adj) * (ab(DJD) + EJm) + ab(DZDEC)).reshape(B, n * dj)
         Kj = float(deg.max()) + 4
-        yield "g:dec.Wp", Link(ZL.T @ dJ, ab(ZL.T) @ dJm, B + Kj)
-        yield "g:dec.bp", Link(dJ.sum(0), dJm.sum(0), B + Kj)
+        dJx = EJx.reshape(B, n * dj)                   # the edge coefficients' allowance on dJ
+        yield "g:dec.Wp", Link(ZL.T @ dJ, ab(ZL.T) @ dJm, B + Kj, extra=np.abs(np.asarray(ZL, f64)).T @ dJx)
+        yield "g:dec.bp", Link(dJ.sum(0), dJm.sum(0), B + Kj, extra=dJx.sum(0))
         Wp = P["dec.Wp"]
-        yield "DZL", Link(dJ @ Wp.T, dJm @ ab(Wp.T), n * dj + Kj)
+        yield "DZL", Link(dJ @ Wp.T, dJm @ ab(Wp.T), n * dj + Kj, extra=dJx @ np.abs(np.asarray(Wp, f64)).T)
         DZL = T(b["DZL"])
         yield "DMS", reparam_bwd(DZL, ab(DZL), 0, "f32")
         DMS = T(b["DMS"])
@@ -715,7 +766,11 @@ def read_plan(model, opt, batch, cfg, fy3: bool):
 # branch of the bf16 plan, every one with partial tiles (tests/test_gpu_own_operands.py).
 # Batch seed, init seed and eps seed are fixed below; the float64 oracle's own
 # pre-activations stay off the kink for them (tests/test_own_operands_cpu.py).
-CASES = (
+# The last field, weighted: every case has a twin "<name>_w" at the loss weights of the
+# weighted-BCE run -- pos_weight and norm of main.py:246-247 from the case's own batch
+# (rounded to float32, as the config struct holds them) and beta = 4 -- so that the sigmoid
+# of the per-edge coefficient, norm in adj_scale and beta in kl_scale are all in play.
+_SHAPES = (
     ("tscale_n200_d16", "tscale", 200, 16, 3, None, False),
     ("tscale_n300_d32", "tscale", 300, 32, 3, None, False),
     ("tscale_n512_d64", "tscale", 512, 64, 2, None, False),
@@ -725,16 +780,28 @@ CASES = (
     ("tref_n300_d32", "tref", 300, 32, 2, None, False),
     ("tscale_n256_d64_k40", "tscale", 256, 64, 2, 40.0, False),
 )
+CASES = tuple(c + (False,) for c in _SHAPES) + tuple((c[0] + "_w",) + c[1:] + (True,) for c in _SHAPES)
 BATCH_SEED, INIT_SEED, EPS_SEED = 11, 2, 9
+WEIGHTED_BETA = 4.0
 
 
-def make_case(topology, n, d, B, kbar):
+def weighted_cfg(cfg, batch):
+    """cfg at the batch's own class balance (main.py:246-247, as float32) and beta = 4."""
+    from snd_vae_amd.input_data import class_balance
+    pw, nm = class_balance(batch.n_graphs, cfg.n_nodes, int(batch.rowptr[-1]))
+    return cfg.replace(weighted_bce=True, pos_weight=float(np.float32(pw)), norm=float(np.float32(nm)),
+                       beta=WEIGHTED_BETA)
+
+
+def make_case(topology, n, d, B, kbar, weighted=False):
     """(cfg, batch, fp32-exact parameter blocks, fp32 eps) of a committed case."""
     from snd_vae_amd.config import tref, tscale
     from snd_vae_amd.data import synthetic_batch
     from snd_vae_amd.params import init_blocks
     cfg = tscale(n, d) if topology == "tscale" else tref(n, d, g_hidden=16, latent=8)
     batch = synthetic_batch(cfg, B, seed=BATCH_SEED, kbar=kbar)
+    if weighted:
+        cfg = weighted_cfg(cfg, batch)
     p = {k: v.astype(np.float32).astype(np.float64) for k, v in init_blocks(cfg, INIT_SEED).items()}
     rows = B if topology == "tref" else B * n
     eps = np.random.default_rng(EPS_SEED).standard_normal((rows, cfg.latent)).astype(np.float32)

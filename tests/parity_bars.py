@@ -23,7 +23,8 @@ Two references sharper than the float64 oracle's bf16 gap:
   terms' of the bf16 z (plan buffers ZSTAGE / ZB); products of bf16 values are exact, so
   a float64 evaluation from those operands differs from the GPU only by fp32
   accumulation and the hardware transcendentals (~1e-7 of the sum): the CE sum within
-  1e-6 of sum |terms|, the accuracy count exact away from |L| < 1e-4.  This is what
+  1e-6 of sum |terms| (at the config's pos_weight / norm, whatever they are), the
+  accuracy count exact away from |L| < 1e-4.  This is what
   catches a wrong logit at pos_weight = 1, which moves adj_cost by ~1e-5 only
   (the round-5 dot2 miscompile).
 * ``e32_grads``: the fp32 error of the reference formulation itself (oracle/ref_torch.py
@@ -119,15 +120,37 @@ def own_structure_dense(jrow):
     return ce, dense_pos, amb
 
 
+def own_structure_sums(jrow, zb, batch, cfg, k32=np.float32):
+    """own_structure from the operands themselves: jrow [B, n, d] the staged rows (log2
+    units), zb [B n, d] the z of the per-edge terms, both float64.  With pw = pos_weight and
+    L_e the logit of edge e,
+        ce = norm (dense + sum_e [(pw - 1) softplus(L_e) - pw L_e] + B n softplus(-1))
+    (the dense kernel sums softplus(L) over every off-diagonal pair; an A = 1 pair's term is
+    pw softplus(-L) = pw (softplus(L) - L), finalize_block applies norm), and the sum of the
+    absolute values of the same terms.  ``k32``: the config holds both weights as floats."""
+    n, B = cfg.n_nodes, batch.n_graphs
+    pw, norm = float(k32(cfg.pos_weight)), float(k32(cfg.norm))
+    dense, dense_pos, amb = own_structure_dense(jrow)
+    rows = np.repeat(np.arange(B * n), np.diff(batch.rowptr))
+    Le = np.einsum("ek,ek->e", zb[rows], zb[batch.colidx])
+    spe = np.maximum(Le, 0.0) + np.log1p(np.exp(-np.abs(Le)))
+    ce = norm * (dense + float(((pw - 1.0) * spe - pw * Le).sum()) + B * n * SOFTPLUS_M1)
+    absum = abs(norm) * (dense + float((abs(pw - 1.0) * spe + abs(pw) * np.abs(Le)).sum()) + B * n * SOFTPLUS_M1)
+    tp = int((Le > 0).sum())
+    amb += int((np.abs(Le) < 1e-4).sum())
+    nnz = int(batch.rowptr[-1])
+    correct = B * n * n - nnz - dense_pos + 2 * tp   # the kernels' count identity
+    return ce, absum, correct, amb
+
+
 def own_structure(model, batch, cfg):
-    """The CE sum (optimizer.py:142-144 summed over pairs, norm = pos_weight = 1) and the
-    accuracy count (main.py:334) from the step's own bf16 operands, in float64.
+    """The CE sum (optimizer.py:142-144 summed over pairs, at the config's pos_weight and
+    norm) and the accuracy count (main.py:334) from the step's own bf16 operands, in float64.
 
     Returns (ce_sum, sum_abs_terms, correct, ambiguous): ce_sum compares with the GPU's
     loss "adj_sum", correct with "correct" (exact up to ``ambiguous`` pairs).
     """
     import torch
-    assert cfg.pos_weight == 1.0 and cfg.norm == 1.0
     n, B, d = cfg.n_nodes, batch.n_graphs, cfg.node_h_size     # d: the width of J (== latent, node latent)
     npad = -(-n // 128) * 128
     dp = 32 if d <= 32 else (64 if d <= 64 else 128)            # snd_zzt.hip zzt_dp
@@ -137,17 +160,7 @@ def own_structure(model, batch, cfg):
     assert not jrow[:, :, d:].any() and not jrow[:, n:, :].any(), "own_structure: staging pad not zero"
     jrow = jrow[:, :, :d]
     zb = model.buffer("ZB", torch.bfloat16)[:B * n * d].view(B * n, d).double().cpu().numpy()
-    ce, dense_pos, amb = own_structure_dense(jrow[:, :n])
-    absum = ce
-    rows = np.repeat(np.arange(B * n), np.diff(batch.rowptr))
-    Le = np.einsum("ek,ek->e", zb[rows], zb[batch.colidx])
-    ce += -float(Le.sum()) + B * n * SOFTPLUS_M1
-    absum += float(np.abs(Le).sum()) + B * n * SOFTPLUS_M1
-    tp = int((Le > 0).sum())
-    amb += int((np.abs(Le) < 1e-4).sum())
-    nnz = int(batch.rowptr[-1])
-    correct = B * n * n - nnz - dense_pos + 2 * tp   # the kernels' count identity
-    return ce, absum, correct, amb
+    return own_structure_sums(jrow[:, :n], zb, batch, cfg)
 
 
 # ---------------------------------------------------------------- fp32 conditioning

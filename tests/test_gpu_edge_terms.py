@@ -8,7 +8,8 @@ of L > 0 for the accuracy.  Both land in the plan's per-tile partials (PEDGE, fl
 {loss, count}).  Here they are recomputed in float64 from the same bf16 z (products of
 bf16 values are exact, so the only device error is the fp32 sum of 64 products and the
 fp32 transcendentals): the loss within 1e-6 of sum |term|, the count exact away from
-|L| < 1e-3.  The end-to-end step tests cannot see a wrong logit at pos_weight = 1 (the
+|L| < 1e-3.  The weighted case also runs norm != 1, which enters after PEDGE: the step's CE
+sum "adj_sum" is held to parity_bars.own_structure at those weights.  The end-to-end step tests cannot see a wrong logit at pos_weight = 1 (the
 reference's effective value): the edge gradient is then -sum z_j,
 independent of L, and the edge loss sum -L is a small part of adj_cost.
 """
@@ -32,14 +33,14 @@ def _gpu(lib_built):
 
 
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("pos_weight", [1.0, 37.5])
+@pytest.mark.parametrize("pos_weight,norm", [(1.0, 1.0), (37.5, 0.52)], ids=["1.0", "37.5"])
 @pytest.mark.parametrize("debug", [0, 262144])   # fused backward head | edge_bf16_kernel chain
-def test_edge_terms_vs_float64(pos_weight, debug):
+def test_edge_terms_vs_float64(pos_weight, norm, debug):
     from snd_vae_amd import _lib
     from snd_vae_amd.model import DeviceBatch, SGCNModelVAE
     from snd_vae_amd.optimizer import OptimizerVAE
     n, B = 1024, 2
-    cfg = dataclasses.replace(tscale(n, 64), pos_weight=pos_weight)
+    cfg = dataclasses.replace(tscale(n, 64), pos_weight=pos_weight, norm=norm)
     batch = synthetic_batch(cfg, B, seed=21)
     p0 = init_blocks(cfg, 4)
     _lib.check(_lib.lib().snd_debug_set(debug))
@@ -68,3 +69,9 @@ def test_edge_terms_vs_float64(pos_weight, debug):
     amb = int(np.sum(np.abs(Lij) < 1e-3))
     ref_tp = int(np.sum(Lij > 0))
     assert abs(got_tp - ref_tp) <= amb, (got_tp, ref_tp, amb)
+    # PEDGE is before norm; the step's CE sum carries it (finalize_block): norm (dense + edge
+    # + rows softplus(-1)) from the step's own operands, within 1e-6 of the sum of |terms|
+    import parity_bars as PB
+    ce, absum, _, _ = PB.own_structure(model, batch, cfg)
+    adj_sum = opt.loss_dict()["adj_sum"]
+    assert abs(adj_sum - ce) <= 1e-6 * absum, (adj_sum, ce, absum)

@@ -26,7 +26,10 @@ Not checkable as a link of their own:
   referred to FU2, with conv3's derived bound carried through; the row-engine cases check
   FY3 / FU3 themselves.
 * EJ, the per-edge terms: never materialised on the fused paths; they enter FDMS's reference
-  from ZB and the CSR (at pos_weight 1 the coefficient is -1: e_i = -sum_j z_j).
+  from ZB and the CSR: e_i = sum_j ((pw - 1) sigmoid(z_i . z_j) - pw) z_j.  Every case runs
+  twice: at the default weights (pos_weight 1: the coefficient is -1, no sigmoid) and, "_w",
+  at its batch's own class balance with beta = 4 -- the per-edge sigmoid of each of the
+  kernels that evaluate it, norm in adj_scale / the CE sum and beta in kl_scale.
 * The transposed staging image and the per-64-row column sums of ZSTAGE, and the per-block
   partial slabs: read only through what is built from them (the CE sum, the gradients).
 * The packed weight images: bitwise against pack_kernel in test_gpu_step.py; every link
@@ -61,12 +64,13 @@ def has_buffer(model, name):
         return False
 
 
-@pytest.mark.parametrize("name,topology,n,d,B,kbar,chain", O.CASES, ids=[c[0] for c in O.CASES])
-def test_step_buffers_on_their_own_operands(name, topology, n, d, B, kbar, chain):
+@pytest.mark.parametrize("name,topology,n,d,B,kbar,chain,weighted", O.CASES, ids=[c[0] for c in O.CASES])
+def test_step_buffers_on_their_own_operands(name, topology, n, d, B, kbar, chain, weighted):
     from snd_vae_amd import _lib
     from snd_vae_amd.model import DeviceBatch, SGCNModelVAE
     from snd_vae_amd.optimizer import OptimizerVAE
-    cfg, batch, p, eps = O.make_case(topology, n, d, B, kbar)
+    cfg, batch, p, eps = O.make_case(topology, n, d, B, kbar, weighted)
+    assert (cfg.pos_weight > 1.0 and cfg.norm != 1.0 and cfg.beta == O.WEIGHTED_BETA) == weighted
     if kbar:
         assert np.diff(batch.rowptr).max() > 32        # rounds past the prefetched neighbours
     _lib.check(_lib.lib().snd_debug_set(CHAIN_BITS if chain else 0))
@@ -96,7 +100,8 @@ def test_step_buffers_on_their_own_operands(name, topology, n, d, B, kbar, chain
     if b.pop("JROW_pad") != 0.0:
         fails.append(("ZSTAGE", "padding rows / columns of the staging image are not zero"))
     res = O.check_all(b, p, batch, cfg, plan)
-    rec = {"case": name, "dec_fused": dec_fused, "head_bwd": head_bwd,
+    rec = {"case": name, "pos_weight": cfg.pos_weight, "norm": cfg.norm, "beta": cfg.beta,
+           "dec_fused": dec_fused, "head_bwd": head_bwd,
            "links": {k: [r, nx] for k, (r, nx) in res.items()}}
     fails += [(k, res[k]) for k in O.failures(res)]
 

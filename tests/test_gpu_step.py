@@ -570,7 +570,20 @@ def test_fused_backward_head_matches_chain(n, d, B):
     262144): d[mu | s], dh and dP1 are bitwise equal and so is every weight gradient
     computed from them; the bias gradient of the [mu | s] head and the edge loss partials
     group rows differently (agree to fp32 / fp64 reassociation), and so do the bias / BN
-    gradients from column partials when the kernel runs 64-row tiles (small batches)."""
+    gradients from column partials when the kernel runs 64-row tiles (small batches).
+
+    This holds at pos_weight = 1 only.  Measured at pos_weight = 20, norm = 0.52, beta = 4 on
+    (512, 64, 2): FDMS differs in 4 of 131072 elements by one bf16 ulp (e.g. [754, 49],
+    [850, 90]; 3 elements at pos_weight = 20 alone, none from norm or beta alone; none seen
+    on (200, 16, 2)).  Both kernels leave `e += coef * z` to the compiler's contraction,
+    which emits an fma for most of the 16 unrolled neighbours of a gather round and a
+    multiply and a packed add for a few -- not the same few in head_bwd_kernel and
+    edge_reparam_bwd_kernel.  coef = -1 makes the product exact, so the default weights
+    cannot see it; both results are within the own-operand bound of FDMS
+    (test_gpu_own_operands.py, the "_w" cases).  Spelling the coefficient and the
+    accumulate as __fmaf_rn in edge_ce_terms' three bf16 callers makes the weighted runs
+    bitwise equal as well; that change and its weighted cases here are not part of the
+    suite yet."""
     from snd_vae_amd import _lib
     from snd_vae_amd.params import init_blocks
     cfg = tscale(n, d)

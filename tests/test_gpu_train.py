@@ -71,7 +71,9 @@ def test_checkpoint_resume(dataset, tmp_path):
 @pytest.mark.parametrize("weighted", [False, True])
 def test_first_step_matches_oracle(dataset, weighted):
     """weighted: row a15 -- the weighted-BCE structure loss with the dataset's
-    pos_weight / norm (`main.py:246-247` over the spanning trees)."""
+    pos_weight / norm (`main.py:246-247` over the spanning trees).  The loss terms and
+    every gradient block against the float64 oracle at the same weights."""
+    from snd_vae_amd import _lib
     from snd_vae_amd.input_data import dataset_class_balance
     from snd_vae_amd.model import DeviceBatch
     from snd_vae_amd.trainer import Trainer
@@ -86,9 +88,19 @@ def test_first_step_matches_oracle(dataset, weighted):
     eps = np.random.default_rng(4).standard_normal((2 * cfg.n_nodes, cfg.latent)).astype(np.float32)
     t.opt.step(t.batches[0], torch.from_numpy(eps).cuda())
     got = t.opt.loss_dict()
-    ref, _, _ = R.forward_backward(p0, [hb.dense_adj(b) for b in range(2)], hb.features,
-                                   hb.feature_truth, hb.spatial_truth, eps.astype(np.float64), cfg,
-                                   want_grads=False)
+    ref, rg, _ = R.forward_backward(p0, [hb.dense_adj(b) for b in range(2)], hb.features,
+                                    hb.feature_truth, hb.spatial_truth, eps.astype(np.float64), cfg)
     for k in ("cost", "adj_cost", "node_cost", "spatial_cost", "kl"):
         assert abs(got[k] - ref[k]) <= 1e-5 * abs(ref[k]) + 1e-7, (k, got[k], ref[k])
     assert isinstance(t.batches[0], DeviceBatch)
+    # every gradient block at the fp32 bar (2e-4 of the block's max-abs); weighted,
+    # this is the fp32 edge_kernel's sigmoid, norm in adj_scale and the CE sum.  The node-latent
+    # step writes every gradient, fused update or not (snd_plan_block_fused is never 1).
+    L = _lib.lib()
+    assert all(L.snd_plan_block_fused(t.model.plan, i) != 1 for i in range(L.snd_plan_num_blocks(t.model.plan)))
+    grads = t.opt.grad_blocks()
+    assert set(grads) == set(rg)
+    worst = {k: float(np.abs(grads[k].reshape(rg[k].shape) - rg[k]).max() / max(np.abs(rg[k]).max(), 1e-30))
+             for k in rg}
+    bad = {k: e for k, e in worst.items() if not e < 2e-4}
+    assert not bad, bad

@@ -177,7 +177,7 @@ def test_rows_rejects_a_range_off_the_row_blocks(what):
 
 
 # ---------------------------------------------------------------- v1 on its own operands
-V1_CASES = tuple(k for k in O.CASES if k[1] == "tscale" and k[5] is None and not k[6])
+V1_CASES = tuple(k[:7] for k in O.CASES if k[1] == "tscale" and k[5] is None and not k[6] and not k[7])   # default weights
 
 
 @pytest.mark.parametrize("name,topology,n,d,B,kbar,chain", V1_CASES, ids=[k[0] for k in V1_CASES])

@@ -17,6 +17,7 @@ from oracle import ref_numpy as R
 from oracle import ref_torch as T
 from snd_vae_amd.config import tref, tscale
 from snd_vae_amd.data import synthetic_batch
+from snd_vae_amd.input_data import class_balance
 from snd_vae_amd.params import init_blocks
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -50,12 +51,16 @@ def test_conv1d_same_matches_torch():
     assert np.allclose(out, ref, atol=1e-12)
 
 
-def _small(n=25, d=8, B=2, seed=3, topology="tscale"):
+def _small(n=25, d=8, B=2, seed=3, topology="tscale", weighted=False):
     if topology == "tref":
         cfg = tref(n, d, g_hidden=12, latent=10, mean_degree=6.0)
     else:
         cfg = tscale(n, d, mean_degree=6.0)
     batch = synthetic_batch(cfg, B, seed=seed)
+    if weighted:   # main.py:246-247 on the case's own adjacency
+        pw, nm = class_balance(B, n, int(batch.rowptr[-1]))
+        assert pw > 1.0 and nm != 1.0
+        cfg = cfg.replace(weighted_bce=True, pos_weight=pw, norm=nm, beta=4.0)
     rng = np.random.default_rng(seed)
     p = {k: v + 0.3 * rng.standard_normal(v.shape) for k, v in init_blocks(cfg, 1).items()}
     eps = rng.standard_normal((B, cfg.latent) if topology == "tref" else (B * n, d))
@@ -63,9 +68,15 @@ def _small(n=25, d=8, B=2, seed=3, topology="tscale"):
     return cfg, batch, p, eps, adj
 
 
-@pytest.mark.parametrize("topology", ["tscale", "tref"])
-def test_oracle_grads_match_torch_autograd(topology):
-    cfg, batch, p, eps, adj = _small(topology=topology)
+# both topologies, at the default loss weights and at the case's own class balance (_small)
+TOPOLOGY_WEIGHTED = pytest.mark.parametrize(
+    "topology,weighted", [("tscale", False), ("tref", False), ("tscale", True), ("tref", True)],
+    ids=["tscale", "tref", "tscale-weighted", "tref-weighted"])
+
+
+@TOPOLOGY_WEIGHTED
+def test_oracle_grads_match_torch_autograd(topology, weighted):
+    cfg, batch, p, eps, adj = _small(topology=topology, weighted=weighted)
     losses, g, _ = R.forward_backward(p, adj, batch.features, batch.feature_truth,
                                       batch.spatial_truth, eps, cfg)
     tp = T.build_params(p, torch.float64)
@@ -80,10 +91,10 @@ def test_oracle_grads_match_torch_autograd(topology):
         assert err < 1e-10, (k, err)
 
 
-@pytest.mark.parametrize("topology", ["tscale", "tref"])
-def test_oracle_finite_differences(topology):
+@TOPOLOGY_WEIGHTED
+def test_oracle_finite_differences(topology, weighted):
     cfg, batch, p, eps, adj = _small(n=12, d=4, B=2 if topology == "tref" else 1, seed=7,
-                                     topology=topology)
+                                     topology=topology, weighted=weighted)
     args = (adj, batch.features, batch.feature_truth, batch.spatial_truth, eps, cfg)
     _, g, _ = R.forward_backward(p, *args)
     rng = np.random.default_rng(0)

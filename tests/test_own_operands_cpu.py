@@ -33,11 +33,18 @@ def rel(a, r):
     return float(np.abs(np.asarray(a) - r).max() / max(np.abs(r).max(), 1e-300))
 
 
-@pytest.mark.parametrize("cfg", [tscale(25, 16), tref(25, 16, g_hidden=16, latent=8)],
-                         ids=["tscale", "tref"])
-def test_links_compose_to_the_oracle(cfg):
+_TS, _TR = tscale(25, 16), tref(25, 16, g_hidden=16, latent=8)
+TOPO_WEIGHTED = pytest.mark.parametrize("cfg,weighted", [(_TS, False), (_TR, False), (_TS, True), (_TR, True)],
+                                        ids=["tscale", "tref", "tscale-weighted", "tref-weighted"])
+
+
+@TOPO_WEIGHTED
+def test_links_compose_to_the_oracle(cfg, weighted):
     B = 2
     batch, p, eps = case(cfg, B)
+    if weighted:
+        cfg = O.weighted_cfg(cfg, batch)
+        assert cfg.pos_weight > 1.0 and cfg.norm != 1.0 and cfg.beta == 4.0
     b = O.run_chain(p, batch, eps, cfg, O.Plan(cfg, True, compose=True), "compose")
     adj = [batch.dense_adj(i) for i in range(B)]
     rl, rg, c = R.forward_backward(p, adj, batch.features, batch.feature_truth, batch.spatial_truth,
@@ -63,24 +70,51 @@ def test_links_compose_to_the_oracle(cfg):
         assert rel(b["g:" + k].reshape(g.shape), g) <= 1e-12, k
 
 
+@TOPO_WEIGHTED
+def test_own_structure_ce_sum_composes_to_the_oracle(cfg, weighted):
+    """parity_bars.own_structure's CE sum and count on the unrounded operands of the composed
+    chain are the oracle's: norm (dense + sum_e[(pw - 1) softplus(L_e) - pw L_e] + B n
+    softplus(-1)) == pairs * adj_cost (the oracle's adj_cost is the mean that already carries
+    norm), to 1e-12."""
+    import parity_bars as PB
+    B, n = 2, cfg.n_nodes
+    batch, p, eps = case(cfg, B)
+    if weighted:
+        cfg = O.weighted_cfg(cfg, batch)
+    b = O.run_chain(p, batch, eps, cfg, O.Plan(cfg, True, compose=True), "compose")
+    rl = R.forward_backward(p, [batch.dense_adj(i) for i in range(B)], batch.features, batch.feature_truth,
+                            batch.spatial_truth, eps.astype(np.float64), cfg, want_grads=False)[0]
+    ce, absum, correct, amb = PB.own_structure_sums(b["JROW"].reshape(B, n, -1), b["ZB"], batch, cfg, k32=O.ident)
+    assert ce == pytest.approx(B * n * n * rl["adj_cost"], rel=1e-12)
+    assert absum >= abs(ce) and correct == rl["correct"]
+    if weighted:   # the weights matter: the unweighted sum is somewhere else entirely
+        ce1 = PB.own_structure_sums(b["JROW"].reshape(B, n, -1), b["ZB"], batch,
+                                    cfg.replace(pos_weight=1.0, norm=1.0), k32=O.ident)[0]
+        assert abs(ce1 - ce) > 1e-3 * absum
+
+
 EMU = {"n200_d16": (tscale(200, 16), 3, False), "n130_d64": (tscale(130, 64), 2, True),
        "n140_d128": (tscale(140, 128), 2, False), "tref_n130_d32": (tref(130, 32, g_hidden=16, latent=8), 2, False)}
 _emu_cache = {}
 
 
-def emulation(key):
-    """(cfg, batch, p, eps, plan, clean buffers) -- computed once per case."""
-    if key not in _emu_cache:
+def emulation(key, weighted=False):
+    """(cfg, batch, p, eps, plan, clean buffers) -- computed once per case.  ``weighted``:
+    at the batch's own pos_weight / norm and beta = 4 (own_operands.weighted_cfg)."""
+    if (key, weighted) not in _emu_cache:
         cfg, B, fy3 = EMU[key]
         batch, p, eps = case(cfg, B)
+        if weighted:
+            cfg = O.weighted_cfg(cfg, batch)
         plan = O.Plan(cfg, fy3)
-        _emu_cache[key] = (cfg, batch, p, eps, plan, O.run_chain(p, batch, eps, cfg, plan, "emulate"))
-    return _emu_cache[key]
+        _emu_cache[key, weighted] = (cfg, batch, p, eps, plan, O.run_chain(p, batch, eps, cfg, plan, "emulate"))
+    return _emu_cache[key, weighted]
 
 
-@pytest.mark.parametrize("key", list(EMU))
-def test_bounds_admit_a_correct_implementation(key):
-    cfg, batch, p, eps, plan, b = emulation(key)
+@pytest.mark.parametrize("key,weighted", [(k, False) for k in EMU] + [(k, True) for k in EMU],
+                         ids=list(EMU) + [k + "-weighted" for k in EMU])
+def test_bounds_admit_a_correct_implementation(key, weighted):
+    cfg, batch, p, eps, plan, b = emulation(key, weighted)
     res = O.check_all(b, p, batch, cfg, plan)
     assert not O.failures(res), {k: res[k] for k in O.failures(res)}
     # the bf16 stores sit at their half ulp: the bound is not slack by more than the factor 2
@@ -213,9 +247,114 @@ def test_one_tile_of_djd_scaled(key):
     assert_caught(fails, order, "DJD")
 
 
-@pytest.mark.parametrize("name,topology,n,d,B,kbar", sorted({(c[0].replace("_chain", ""),) + c[1:6] for c in O.CASES}))
-def test_committed_seeds_keep_the_oracle_off_the_kink(name, topology, n, d, B, kbar):
-    cfg, batch, p, eps = O.make_case(topology, n, d, B, kbar)
+# ---- planted faults in how the step uses pos_weight / norm / beta: each is ONE change to
+# the weighted emulation (own_operands.edge_sigmoid / edge_coef / loss_scales, the three
+# places the emulation reads the weights through), run on the chain's own upstream buffers.
+def _sig_negated(x):                                  # (a) sigmoid(-L) for sigmoid(L)
+    return _EDGE_SIGMOID(-x)
+
+
+def _sig_no_e(x):                                     # (b) r instead of e r on the negative branch
+    e = np.exp(-np.abs(x))
+    return 1 / (1 + e)
+
+
+def _coef_pw(x, pw):                                  # (c) pw instead of pw - 1 on the sigmoid
+    return np.full(x.shape, -pw, x.dtype) + pw * O.edge_sigmoid(x)
+
+
+def _coef_early_out(x, pw):                           # (f) the pw == 1 early-out's coefficient
+    return np.full(x.shape, -pw, x.dtype)
+
+
+def _scales_no_norm(cfg, B, n, RH, L, k32):           # (d) adj_scale without norm
+    pw, _, klc = _LOSS_SCALES(cfg, B, n, RH, L, k32)
+    return pw, k32(2.0 / (float(B) * n * n)), klc
+
+
+def _scales_no_beta(cfg, B, n, RH, L, k32):           # (e) kl_scale without beta
+    pw, adj, _ = _LOSS_SCALES(cfg, B, n, RH, L, k32)
+    return pw, adj, k32(1.0 / (float(RH) * L))
+
+
+_EDGE_SIGMOID, _LOSS_SCALES = O.edge_sigmoid, O.loss_scales
+FAULTS = {"a_sigmoid_of_minus_L": ("edge_sigmoid", _sig_negated), "b_r_for_e_r": ("edge_sigmoid", _sig_no_e),
+          "c_pw_for_pw_minus_1": ("edge_coef", _coef_pw), "d_adj_scale_without_norm": ("loss_scales", _scales_no_norm),
+          "e_kl_scale_without_beta": ("loss_scales", _scales_no_beta), "f_early_out_coef": ("edge_coef", _coef_early_out)}
+# the links that read dJ (and the scales) directly; the first is the one that must fail
+FIRST = {False: ("FDMS", "g:enc.bms"), True: ("g:dec.Wp", "g:dec.bp", "DZL", "DMS")}
+
+
+def planted(key, fault, monkeypatch):
+    """The weighted emulation with ``fault`` planted: the links that read dJ / the scales
+    directly hold what the faulty step computes from the (clean) upstream buffers, everything
+    downstream is computed from those.  Returns (failing links, step order, first targets)."""
+    cfg, batch, p, eps, plan, clean = emulation(key, True)
+    targets = FIRST[plan.tref]
+    with monkeypatch.context() as m:
+        m.setattr(O, FAULTS[fault][0], FAULTS[fault][1])
+        faulty = O.run_chain(p, batch, eps, cfg, plan, "emulate")
+    order = []
+
+    def hook(name, v, b):
+        order.append(name)
+        return faulty[name] if name in targets else None
+
+    b = O.run_chain(p, batch, eps, cfg, plan, "emulate", perturb=hook)
+    up = order[:order.index(targets[0])]
+    assert all(np.array_equal(b[k], clean[k]) and np.array_equal(faulty[k], clean[k]) for k in up)
+    return O.failures(O.check_all(b, p, batch, cfg, plan)), order, targets
+
+
+def assert_fault_caught(fails, order, targets):
+    assert targets[0] in fails, (targets[0], fails)
+    up = [k for k in fails if order.index(k) < order.index(targets[0])]
+    assert not up, ("a check upstream of the planted fault failed", up)
+    # everything downstream is referred to its own stored operands: nothing else may move
+    assert set(fails) <= set(targets), fails
+
+
+@pytest.mark.parametrize("key", ["n200_d16", "n130_d64"])
+@pytest.mark.parametrize("fault", list(FAULTS))
+def test_planted_fault_in_the_loss_weights_fails_fdms(key, fault, monkeypatch):
+    fails, order, targets = planted(key, fault, monkeypatch)
+    assert targets[0] == "FDMS"
+    assert_fault_caught(fails, order, targets)
+
+
+@pytest.mark.parametrize("fault", ["a_sigmoid_of_minus_L", "c_pw_for_pw_minus_1"])
+def test_planted_fault_on_the_graph_latent(fault, monkeypatch):
+    """Graph latent: dJ first feeds the projection's weight gradient g:dec.Wp.  Its edge
+    logits at initialisation are small (|L| < 0.1, sigmoid within 0.025 of 1/2), so (a), the
+    sign inside the sigmoid, moves a coefficient by at most (pw - 1) 0.05; summed into
+    g:dec.Wp that is still thousands of bounds, so (a) fails the link here as well.  (c) --
+    pw for pw - 1, which moves every coefficient by sigmoid(L) ~ 1/2 -- is asserted beside
+    it, should a case with smaller logits ever let (a) through."""
+    fails, order, targets = planted("tref_n130_d32", fault, monkeypatch)
+    assert targets[0] == "g:dec.Wp"
+    assert_fault_caught(fails, order, targets)
+
+
+def test_weighted_emulation_takes_both_sigmoid_branches():
+    """The planted faults (a) / (b) need edges on both branches of edge_ce_terms, and logits
+    large enough for the sigmoid to matter: true at the emulated cases' own operands."""
+    for key in ("n200_d16", "n130_d64"):
+        cfg, batch, p, eps, plan, b = emulation(key, True)
+        rows = np.repeat(np.arange(len(batch.rowptr) - 1), np.diff(batch.rowptr))
+        Le = (b["ZB"][rows] * b["ZB"][batch.colidx]).sum(1)
+        assert (Le < -1).mean() > 0.02 and (Le > 1).mean() > 0.02, (key, (Le < -1).mean(), (Le > 1).mean())
+
+
+_SEEDED = sorted({(c[0].replace("_chain", ""),) + c[1:6] + c[7:] for c in O.CASES}, key=lambda c: c[0])
+
+
+@pytest.mark.parametrize("name,topology,n,d,B,kbar,weighted", _SEEDED,
+                         ids=["-".join(str(v) for v in c[:6]) for c in _SEEDED])
+def test_committed_seeds_keep_the_oracle_off_the_kink(name, topology, n, d, B, kbar, weighted):
+    """(The forward pre-activations do not depend on the loss weights; the "_w" twins are
+    asserted all the same.)"""
+    cfg, batch, p, eps = O.make_case(topology, n, d, B, kbar, weighted)
+    assert (cfg.pos_weight != 1.0 and cfg.norm != 1.0 and cfg.beta == O.WEIGHTED_BETA) == weighted
     adj = [batch.sparse_adj(i) for i in range(B)]
     _, _, c = R.forward_backward(p, adj, batch.features, batch.feature_truth, batch.spatial_truth,
                                  eps.astype(np.float64), cfg, want_grads=False, row_chunk=512)
